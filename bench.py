@@ -5,8 +5,15 @@
 A "step" = one batched layer-descent + layer-0 beam search of `--batch` query
 vectors already resident in HBM, through the C ABI (mhnsw_search_device).
 
-Multi-GPU (one process per GPU, torchrun).  Two layouts, both measured by
-default (the headline `value` is the replica layout; the shard layout is the
+A plain run builds the index, measures recall@10 against the exact path, warms
+up, times `--steps` steps and prints the line (`value`, `ms_per_step`, the
+search and build rooflines from the counters of those same runs).  Every other
+measurement below runs only with `--full`.  `--dump-outputs DIR` writes the
+lists the last timed step returned as DIR/<name>.npy; the data and the queries
+are seeded, so two runs with the same arguments search the same inputs.
+
+Multi-GPU (one process per GPU, torchrun).  Two layouts, both measured with
+`--full` (the headline `value` is the replica layout; the shard layout is the
 `shard` object of the same JSON line):
   replica: every rank holds the full 1M-vector index and serves its own slice
       of the query stream; no data-path collective (per-GPU work fixed =>
@@ -23,8 +30,9 @@ default (the headline `value` is the replica layout; the shard layout is the
 Also reported: recall@10 against the exact (MFMA brute-force) path, build
 throughput of the batched insert, the search kernel's roofline (HBM-bound;
 algorithmic bytes from in-kernel distance-evaluation / expansion counters), and
-the CPU restatement (oracle/, same algorithm, same graph) timed on a bounded
-sample on the host.
+with `--full` the operating points, the secondary configs and the CPU
+restatement (oracle/, same algorithm, same graph) timed on a bounded sample on
+the host.
 """
 import argparse
 import json
@@ -54,8 +62,16 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="also run every side leg (shard layout, shard emulation, operating / expansion / batch "
+                        "points, distance sweep, oracle parity + CPU baseline, secondary configs); without it the "
+                        "run builds the index, measures recall, times the steps and prints the line, and the "
+                        "options that shape the side legs have no effect")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (keys, dist, n of every query) as DIR/<name>.npy")
     p.add_argument("--mode", choices=["replica", "shard"], default="replica",
-                   help="headline layout; with replica the shard layout is measured too (--no-shard-leg skips it)")
+                   help="headline layout; with --full and replica the shard layout is measured too "
+                        "(--no-shard-leg skips it)")
     p.add_argument("--no-shard-leg", action="store_true")
     p.add_argument("--nbase", type=int, default=1_000_000, help="vectors of the replica index")
     p.add_argument("--total-rows", type=int, default=10_000_000,
@@ -113,7 +129,35 @@ def parse():
     p.add_argument("--one-gpu", action="store_true", help="map every rank to cuda:0 (multi-rank rehearsal)")
     p.add_argument("--pmc-json", default=os.path.join(ROOT, "profiles", "r06_pmc_search.json"))
     p.add_argument("--pmc-build-json", default=os.path.join(ROOT, "profiles", "r06_pmc_build.json"))
-    return p.parse_args()
+    a = p.parse_args()
+    if not a.full:  # a plain run: the headline only, every side leg off
+        a.no_shard_leg, a.emulate_shards, a.cpu_seconds = True, 0, 0.0
+        a.configs = a.ef_sweep = a.shard_ef_sweep = a.batch_sweep = ""
+    return a
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, keys, dists, n, rank=0):
+    """The lists the last timed step returned, as <path>/{keys,dist,n}.npy (rank
+    r > 0: <name>.rank<r>.npy): keys as float64 (exact below 2^53), distances and
+    counts as float32; entries past a query's count read -1 / 0.  A result larger
+    than DUMP_MAX_BYTES is cut to a fixed, seeded sample of its queries (rows.npy
+    holds their indices)."""
+    keys, dists, n = (x.cpu().numpy() for x in (keys, dists, n))
+    B, k = keys.shape
+    live = np.arange(k)[None, :] < n[:, None]
+    arrays = {"keys": np.where(live, keys, -1).astype(np.float64),
+              "dist": np.where(live, dists, 0).astype(np.float32), "n": n.astype(np.float32)}
+    rows = DUMP_MAX_BYTES // (12 * k + 12)
+    if B > rows:
+        sel = np.sort(np.random.default_rng(0).choice(B, rows, replace=False))
+        arrays = {name: v[sel] for name, v in arrays.items()}
+        arrays["rows"] = sel.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), v)
 
 
 def gen_vectors(n, dim, seed, intrinsic, clusters, device, metric, offset=0):
@@ -556,7 +600,7 @@ def main():
         g.add_device(keys, X.data_ptr(), nrows, a.dim)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        if sweep is None and rank == 0 and nrows == a.nbase:
+        if a.full and sweep is None and rank == 0 and nrows == a.nbase:
             sweep = sweep_bench(X)
         del X
         return g, dt, g.stats()
@@ -599,18 +643,21 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        last = None
         for _ in range(a.steps):
-            step()
+            last = step()
             kernel_ms.append(g.last_kernel_ms())
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         elapsed = time.perf_counter() - t0
         g.device_status()  # kernel-side errors of the asynchronous searches
+        if a.dump_outputs and last is not None:  # the last step's lists, before a later leg reuses the buffers
+            last = tuple(x.clone() for x in last)
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device)
         if world > 1:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        return tt.item(), kernel_ms, g.stats()
+        return tt.item(), kernel_ms, g.stats(), last
 
     def mean_over_ranks(x):
         if world == 1:
@@ -706,7 +753,7 @@ def main():
         tk, td, tn = G.run(Q[:ngt], H.MODE_EXACT, 0)
         torch.cuda.synchronize()
         recall = mean_over_ranks(recall_at_k(res_k[:ngt], res_n[:ngt], tk, tn, a.k))
-        elapsed, kernel_ms, st = timed_steps(step, g)
+        elapsed, kernel_ms, st, last = timed_steps(step, g)
 
     mark("replica_index_and_headline")
     # ---- shard layout: rank r owns rows [r*nbase, (r+1)*nbase) of one dataset --------
@@ -740,12 +787,12 @@ def main():
         ek, ed, en = sharded_search(engine_local_search(gs, a.k, H.MODE_EXACT, 0), Qs[:ngt], a.k)
         torch.cuda.synchronize()
         srecall = mean_over_ranks(recall_at_k(sk[:ngt], sn[:ngt], ek, en, a.k))
-        s_el, s_kms, s_st = timed_steps(sstep, gs)
+        s_el, s_kms, s_st, s_last = timed_steps(sstep, gs)
         skms = float(np.mean(s_kms))
         # the step's phases (HIP events on torch's stream): local search, the packed
         # all-gather (RCCL), the GPU merge -- 0 at one rank (nothing is exchanged)
         ph = {"search": [], "all_gather": [], "merge": []}
-        for _ in range(3):
+        for _ in range(3 if a.full else 0):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             ev[0].record()
             lk, ld, ln = engine_local_search(gs, a.k, H.MODE_BEAM, a.ef)(Qs)
@@ -760,7 +807,7 @@ def main():
             torch.cuda.synchronize()
             for name, i in (("search", 0), ("all_gather", 1), ("merge", 2)):
                 ph[name].append(ev[i].elapsed_time(ev[i + 1]))
-        phases = {f"{k_}_ms": round(float(np.mean(v)), 4) for k_, v in ph.items()}
+        phases = {f"{k_}_ms": round(float(np.mean(v)), 4) if v else None for k_, v in ph.items()}
         # operating points of the shard layout (recall vs the sharded exact top-k, QPS of
         # the whole step: search + exchange + merge, max over ranks), so that one 10M
         # index (N = 1) and 8 shards of 1.25M (N = 8) compare at equal recall
@@ -808,6 +855,7 @@ def main():
             shard_out["emulated"] = emu
         if shard_only:
             g, build_s, bstats, recall, elapsed, kernel_ms, st = gs, sbuild_s, sbstats, srecall, s_el, s_kms, s_st
+            last = s_last
             Q, S = Qs, Searcher(gs, a.batch, a.k, a.dim, device)
             tk, tn = ek, en
 
@@ -830,6 +878,8 @@ def main():
     g_rows = (shard_out["rows_per_shard"] if shard_only else a.nbase)
     queries_done = a.batch * a.steps * (1 if shard else world)
     qps = queries_done / elapsed
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, *last, rank=rank)
 
     # roofline of the search kernel (per launch = one step on this GPU)
     cap0 = a.M0 + 1

@@ -7,7 +7,7 @@
 #     smoke              __graft_entry__.smoke()
 #     suite              the whole GPU suite (pytest -m gpu)
 #     test:A,B,...       pytest -m gpu with the arguments A B ... (paths, -k EXPR)
-#     bench[:A,B,...]    bench.py (the driver's command: --gpus 1 --steps 20 --warmup 5) plus A B ...
+#     bench[:A,B,...]    the full bench line (bench.py --full --gpus 1 --steps 20 --warmup 5) plus A B ...
 #     rehearse2          the driver's N=2 command as 2 gloo ranks on this one GPU
 #     prof[:A,B,...]     tools/profile_round.sh TAG (kernel trace + FETCH/WRITE PMC) with A B ...
 #     py:SCRIPT[,A,...]  python SCRIPT A ... (a tools/ probe)
@@ -36,9 +36,9 @@ for step in "$@"; do
     smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$log" 2>&1 ;;
     suite) timeout -k 10 1100 $PYT tests > "$log" 2>&1 ;;
     test) timeout -k 10 900 $PYT $args > "$log" 2>&1 ;;
-    bench) timeout -k 10 900 python -u bench.py --gpus 1 --steps 20 --warmup 5 $args > "$O/$i.bench.json" 2> "$log" ;;
+    bench) timeout -k 10 900 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 $args > "$O/$i.bench.json" 2> "$log" ;;
     rehearse2) timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --one-gpu \
+        --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 5 --warmup 2 --one-gpu \
         --backend gloo $args > "$O/$i.rehearse2.json" 2> "$log" ;;
     prof) timeout -k 10 1100 bash tools/profile_round.sh "$TAG/prof$i" $args > "$log" 2>&1 ;;
     py) timeout -k 10 900 python -u $args > "$log" 2>&1 ;;
