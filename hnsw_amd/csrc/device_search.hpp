@@ -313,7 +313,9 @@ __device__ __forceinline__ int vis_any_cap(int vsize) { return vsize < 0 ? VIS16
 // A), every list entry moved down by the candidates ranked at or before it,
 // and both written into A at their new places and read back (distances, then
 // ids).  A candidate whose distance equals a listed one (the same row met
-// again, or equal rows) or any infinite distance sends the buffer through
+// again, or equal rows), any infinite distance, or a candidate that is worse
+// than every listed entry (it beat the worst entry before the step, and an
+// earlier flush of the same step lowered that) sends the buffer through
 // bl_insert instead.  LDS scratch M: A = M[0, 512) (the list), the k <= 64
 // candidates in M[512 + j] (distance) and M[576 + j] (id), in arrival order.
 constexpr int BL_MERGE_WORDS = 640;
@@ -345,9 +347,14 @@ __device__ __forceinline__ void bl_merge(BList<R>& L, int ef, int k, float* M) {
             if (r * 64 + lane < ef) A[r * 64 + lane] = L.d[r];
         wave_sync();
         if (lane < k) {
-            // lower bound over A[0, ef); a candidate is below the worst entry, so lb < ef
+            // lower bound over A[0, ef], so that lb can reach ef: a candidate beat the
+            // worst entry before the step, but a step's earlier flush (XW > 1, bk + cnt
+            // > 64) may have lowered the worst entry below it.  Such a candidate must be
+            // dropped, not placed on the last entry: lb == ef sends the buffer through
+            // bl_insert, which drops it.  (The steps add up to 128 R - 1 >= ef; from
+            // R * 32 they stopped at 64 R - 1 and never compared A[ef - 1] at ef = 64 R.)
 #pragma unroll
-            for (int step = R * 32; step >= 1; step >>= 1) {
+            for (int step = R * 64; step >= 1; step >>= 1) {
                 const int t = lb + step - 1;
                 if (t < ef && A[t] < d) lb += step;
             }

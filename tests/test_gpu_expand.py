@@ -49,16 +49,18 @@ def _with(g, **opts):
 @pytest.mark.parametrize("ef", [10, 64, 200, 512])
 def test_search_expand_matches_oracle(H, O, built, metric, xw, ef):
     g, o, Q = built[metric]
+    ks = (10, ef) if ef > 128 else (10,)  # the wide lists (bl_merge) also whole
     o.set_search_expand(xw)
-    rk, rd, rn = o.search(Q, 10, mode=O.MODE_BEAM, ef=ef)
+    ref = {k: o.search(Q, k, mode=O.MODE_BEAM, ef=ef) for k in ks}
     o.set_search_expand(1)
     old = _with(g, search_expand=xw)
     try:
         for screen in (1, 0):
             for compact in (1, 0):
                 _with(g, screen=screen, vis_compact=compact)
-                gk, gd, gn = g.search_arrays(Q, 10, mode=H.MODE_BEAM, ef=ef)
-                _same_results(gk, gd, gn, rk, rd, rn)
+                for k in ks:
+                    gk, gd, gn = g.search_arrays(Q, k, mode=H.MODE_BEAM, ef=ef)
+                    _same_results(gk, gd, gn, *ref[k])
     finally:
         _with(g, screen=1, vis_compact=1, **old)
 

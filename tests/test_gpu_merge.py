@@ -2,8 +2,8 @@
 (device_search.hpp bl_merge, beam_layer MERGE): each layer-0 step's candidates
 are merged into the list at once instead of one bl_insert each.  The list after
 a step is the best ef of its entries and the step's candidates whatever the
-order, so the results must equal the oracle's one-at-a-time restatement bit for
-bit -- on the fast path (distinct distances), on the fallback taken when a
+order, so the results (the first 10 and the whole list, k = ef) must equal the
+oracle's one-at-a-time restatement bit for bit -- on the fast path (distinct distances), on the fallback taken when a
 candidate's distance equals a listed one (duplicate rows: every vector stored
 three times under different keys), for XW 1 / 2 / 4, both metrics, and with
 the merge scratch placed after the compact set, after the 32-bit set, and after
@@ -43,15 +43,16 @@ def dup_built(H, O):
 
 def _check(H, O, g, o, Q, xw, ef, **opts):
     o.set_search_expand(xw)
-    rk, rd, rn = o.search(Q, 10, mode=O.MODE_BEAM, ef=ef)
+    ref = {k: o.search(Q, k, mode=O.MODE_BEAM, ef=ef) for k in (10, ef)}  # the first 10 and the whole list
     o.set_search_expand(1)
     old = {k: g.get_option(k) for k in ("search_expand", *opts)}
     try:
         g.set_option("search_expand", xw)
         for k, v in opts.items():
             g.set_option(k, v)
-        gk, gd, gn = g.search_arrays(Q, 10, mode=H.MODE_BEAM, ef=ef)
-        _same_results(gk, gd, gn, rk, rd, rn)
+        for k in (10, ef):
+            gk, gd, gn = g.search_arrays(Q, k, mode=H.MODE_BEAM, ef=ef)
+            _same_results(gk, gd, gn, *ref[k])
     finally:
         for k, v in old.items():
             g.set_option(k, v)

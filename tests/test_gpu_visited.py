@@ -156,6 +156,7 @@ def test_compact_visited_set(H, O, wide):
     forgets), the compact set resets less and evaluates less."""
     g, o, Q = wide
     rk, rd, rn = o.search(Q, 10, mode=O.MODE_BEAM, ef=512)
+    whole = o.search(Q, 512, mode=O.MODE_BEAM, ef=512)
     st = {}
     for c in (0, 1):
         g.set_option("vis_compact", c)
@@ -163,6 +164,7 @@ def test_compact_visited_set(H, O, wide):
         gk, gd, gn = g.search_arrays(Q, 10, mode=H.MODE_BEAM, ef=512)
         st[c] = g.stats()
         _same_results(gk, gd, gn, rk, rd, rn)
+        _same_results(*g.search_arrays(Q, 512, mode=H.MODE_BEAM, ef=512), *whole)  # the whole list (k = ef)
     g.set_option("vis_compact", 1)
     print({c: (s["visited_resets"], s["search_dist_evals"]) for c, s in st.items()})
     assert st[0]["visited_resets"] >= len(Q), st
