@@ -1229,6 +1229,9 @@ int mhnsw_set_option(mhnsw_index* h, const char* name, int64_t v) {
     } else if (n == "beam_mw_max_b") {
         if (v < 0) return fail(h, MHNSW_EINVAL, "beam_mw_max_b must be >= 0");
         h->beam_mw_max_b = v;
+    } else if (n == "beam_lds_min_ef") {
+        if (v < 65 || v > 513) return fail(h, MHNSW_EINVAL, "beam_lds_min_ef must be in [65, 513]");
+        h->beam_lds_min_ef = (int)v;
     } else if (n == "upper_ef") {
         if (v < 1 || v > 64) return fail(h, MHNSW_EINVAL, "upper_ef must be in [1, 64]");
         h->upper_ef = (int)v;
@@ -1302,6 +1305,7 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
     else if (n == "compat_waves") *v = h->compat_waves;
     else if (n == "upper_ef") *v = h->upper_ef;
     else if (n == "beam_mw_max_b") *v = h->beam_mw_max_b;
+    else if (n == "beam_lds_min_ef") *v = h->beam_lds_min_ef;
     else if (n == "build_mw_max") *v = h->build_mw_max;
     else if (n == "screen") *v = h->screen;
     else if (n == "fuse_descent") *v = h->fuse_descent;

@@ -2,7 +2,9 @@
 // dimension-configuration list, shared by search.hip (dispatch) and the
 // beam_*.hip translation units that instantiate it per configuration (split
 // so that the kernel's 4 list widths x 2 screen modes x 10 configurations
-// compile in parallel).
+// compile in parallel).  Past the register lists (max(ef, k) > 512) the same
+// search runs on a list held in LDS: k_search_beam_lds, instantiated per
+// configuration, screen mode and XW in beam_w*.hip.
 #pragma once
 #include "device_search.hpp"
 #include "engine.hpp"
@@ -36,11 +38,10 @@ int launch_beam_cfg(const SearchArgs& a, hipStream_t s);
 // the visited set's LDS words (the merge scratch follows it)
 __host__ __device__ inline int beam_vis_words(const SearchArgs& a) { return a.vis16 ? VIS16_WORDS : a.vis_n; }
 
-template <class C, int R, int G, bool SCREEN, int XW, class BEv>
-__device__ __forceinline__ void beam_query(const SearchArgs& a, int64_t b, const QReg<C>& q, float qn, uint32_t* smem,
-                                           WaveStats& st, const BEv& bev) {
-    const int lane = lane_id();
-    const int vsz = a.vis16 ? -1 : a.vis_n;  // (beam_layer: < 0 selects the compact set)
+// the greedy descent (ef = upper_ef) from the top layer's entry to layer 0's
+template <class C, int G, bool SCREEN, class BEv>
+__device__ __forceinline__ uint32_t beam_descend(const SearchArgs& a, const QReg<C>& q, float qn, uint32_t* smem,
+                                                 int vsz, WaveStats& st, const BEv& bev) {
     uint32_t ep = a.entry;
     {
         BList<1> L1;
@@ -57,9 +58,29 @@ __device__ __forceinline__ void beam_query(const SearchArgs& a, int64_t b, const
             if (id != EMPTY_ID) ep = id & ID_MASK;
         }
     }
+    if (a.g.layers[0].deg[ep] == -2) ep = (uint32_t)a.layer_entry[0];
+    return ep;
+}
+
+// rows [nvalid, k) of query b's outputs: no result
+__device__ __forceinline__ void beam_pad_out(const SearchArgs& a, int64_t b, int nvalid) {
+    const int lane = lane_id();
+    for (int i = nvalid + lane; i < a.k; i += 64) {
+        a.out_keys[b * a.k + i] = (int64_t)-1;
+        a.out_dist[b * a.k + i] = __int_as_float(0x7f800000);
+        if (a.out_ids) a.out_ids[b * a.k + i] = -1;
+    }
+    if (lane == 0) a.out_n[b] = nvalid;
+}
+
+template <class C, int R, int G, bool SCREEN, int XW, class BEv>
+__device__ __forceinline__ void beam_query(const SearchArgs& a, int64_t b, const QReg<C>& q, float qn, uint32_t* smem,
+                                           WaveStats& st, const BEv& bev) {
+    const int lane = lane_id();
+    const int vsz = a.vis16 ? -1 : a.vis_n;  // (beam_layer: < 0 selects the compact set)
+    const uint32_t ep = beam_descend<C, G, SCREEN>(a, q, qn, smem, vsz, st, bev);
     BList<R> L;
     const int efl = a.ef > a.k ? a.ef : a.k;
-    if (a.g.layers[0].deg[ep] == -2) ep = (uint32_t)a.layer_entry[0];
     // lists of 256 / 512 entries merge each step's candidates at once, with the
     // LDS past the visited set as scratch (launch_beam_t sizes the LDS for it;
     // the default compact set leaves room in the 20 KiB a 2-wave SIMD allows)
@@ -83,13 +104,7 @@ __device__ __forceinline__ void beam_query(const SearchArgs& a, int64_t b, const
         }
         nvalid += __popcll(m);
     }
-    nvalid = min(nvalid, a.k);
-    for (int i = nvalid + lane; i < a.k; i += 64) {
-        a.out_keys[b * a.k + i] = (int64_t)-1;
-        a.out_dist[b * a.k + i] = __int_as_float(0x7f800000);
-        if (a.out_ids) a.out_ids[b * a.k + i] = -1;
-    }
-    if (lane == 0) a.out_n[b] = nvalid;
+    beam_pad_out(a, b, min(nvalid, a.k));
 }
 
 __device__ __forceinline__ void beam_stats(const SearchArgs& a, const WaveStats& st) {
@@ -199,6 +214,73 @@ static int launch_beam_t(const SearchArgs& a, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ---------------------------------------------------------------------------
+// wide lists (beam_lds_min_ef <= max(ef, k) <= LL_MAX_EF): the layer-0 list in
+// LDS (device_search.hpp LList) behind the visited set; one wave per query at
+// every batch size and every XW.  The descent, the step structure, the screen
+// and the visited set are k_search_beam's (beam_layer_l over the other list),
+// so the results are the register lists' at equal ef.
+// ---------------------------------------------------------------------------
+template <class C, int G, bool SCREEN, int XW>
+__global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_search_beam_lds(SearchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const int64_t b = blockIdx.x;
+    if (b >= a.B) return;
+    const int lane = lane_id();
+    QReg<C> q;
+    load_query(q, a.q + (size_t)b * C::PITCH);
+    const float qn = query_norm(q);
+    WaveStats st;
+    const WaveBatch bev;
+    const int vsz = a.vis16 ? -1 : a.vis_n;
+    const uint32_t ep = beam_descend<C, G, SCREEN>(a, q, qn, smem, vsz, st, bev);
+    const int efl = a.ef > a.k ? a.ef : a.k;
+    LList L;
+    ll_place(L, smem + ((beam_vis_words(a) + 3) & ~3), efl);
+    beam_layer_l<C, LList, G, false, SCREEN, XW, true, WaveBatch>(a.g, 0, ep, efl, q, qn, L, smem, vsz, st, bev, nullptr);
+    // the first k live entries (deleted rows route the search but are never returned)
+    int nvalid = 0;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int c = 0; c < L.n && nvalid < a.k; c += 64) {
+        const int idx = c + lane;
+        const uint32_t w = idx < L.n ? L.i[idx] : EMPTY_ID;
+        const uint32_t id = w & ID_MASK;
+        const bool ok = w != EMPTY_ID && !is_dead(a.g, id);
+        const unsigned long long m = __ballot(ok);
+        const int pos = nvalid + __popcll(m & below);
+        if (ok && pos < a.k) {
+            a.out_keys[b * a.k + pos] = a.g.keys[id];
+            a.out_dist[b * a.k + pos] = L.d[idx];
+            if (a.out_ids) a.out_ids[b * a.k + pos] = (int32_t)id;
+        }
+        nvalid += __popcll(m);
+    }
+    beam_pad_out(a, b, min(nvalid, a.k));
+    beam_stats(a, st);
+}
+
+// the wide tier's dynamic LDS: the visited set, then the list
+inline size_t beam_lds_bytes(const SearchArgs& a) {
+    const int efl = a.ef > a.k ? a.ef : a.k;
+    return (size_t)4 * (size_t)(((beam_vis_words(a) + 3) & ~3) + ll_words(efl));
+}
+constexpr size_t BEAM_LDS_MAX_BYTES = 64 * 1024;  // a workgroup's LDS without an opt-in attribute
+
+// -2: the visited set and the list do not fit a workgroup's LDS (an explicit
+// vis_entries too large for this ef); -4: past the list's capacity
+template <class C, int G, int XW>
+static int launch_beam_lds_t(const SearchArgs& a, hipStream_t s) {
+    const int efl = a.ef > a.k ? a.ef : a.k;
+    if (efl > LL_MAX_EF) return -4;
+    const size_t lds = beam_lds_bytes(a);
+    if (lds > BEAM_LDS_MAX_BYTES) return -2;
+    if (a.g.h16)
+        hipLaunchKernelGGL((k_search_beam_lds<C, G, true, XW>), dim3((unsigned)a.B), dim3(64), lds, s, a);
+    else
+        hipLaunchKernelGGL((k_search_beam_lds<C, G, false, XW>), dim3((unsigned)a.B), dim3(64), lds, s, a);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // group width G of configuration (L, V), from MH_FOR_EACH_CFG
 template <int L, int V>
 constexpr int beam_group() {
@@ -219,6 +301,12 @@ int launch_beam_cfg(const SearchArgs& a, hipStream_t s) {
     constexpr int GW = MH_BEAM_WIDE_G > 0 && MH_BEAM_WIDE_G < G ? MH_BEAM_WIDE_G : G;
     if (efl <= 512) return launch_beam_t<Cfg<L, V>, 8, GW, XW>(a, s);
     return -4;
+}
+
+// instantiated per XW in beam_wa-wc.hip
+template <int L, int V, int XW>
+int launch_beam_lds_cfg(const SearchArgs& a, hipStream_t s) {
+    return launch_beam_lds_t<Cfg<L, V>, beam_group<L, V>(), XW>(a, s);
 }
 
 }  // namespace mh

@@ -1,0 +1,11 @@
+// beam_w2a.hip -- k_search_beam_lds instantiations (beam.hpp: the LDS-resident list,
+// max(ef, k) past the register lists) with 2 entries expanded per layer-0 step for 16x1 .. 64x3
+#include "beam.hpp"
+
+namespace mh {
+template int launch_beam_lds_cfg<16, 1, 2>(const SearchArgs&, hipStream_t);
+template int launch_beam_lds_cfg<32, 1, 2>(const SearchArgs&, hipStream_t);
+template int launch_beam_lds_cfg<64, 1, 2>(const SearchArgs&, hipStream_t);
+template int launch_beam_lds_cfg<64, 2, 2>(const SearchArgs&, hipStream_t);
+template int launch_beam_lds_cfg<64, 3, 2>(const SearchArgs&, hipStream_t);
+}  // namespace mh

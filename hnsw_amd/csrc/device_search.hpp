@@ -400,6 +400,228 @@ __device__ __forceinline__ void bl_merge(BList<R>& L, int ef, int k, float* M) {
     wave_sync();
 }
 
+// where beam_layer's MERGE steps buffer their candidates: distances in
+// buf[0, 64), ids in buf[64, 128), in arrival order
+template <int R>
+__device__ __forceinline__ float* bl_cbuf(BList<R>&, float* mrg) {
+    return mrg + 512;
+}
+
+// after a visited reset the list's members stay visited: they are the
+// neighbourhood the next expansions keep meeting (fewer re-evaluations).
+// Returns the ids recorded.
+template <int R>
+__device__ __forceinline__ int bl_seed(const BList<R>& L, uint32_t* vis, int vsize) {
+    int seeded = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const uint32_t id = L.i[r];
+        const bool ins = id != EMPTY_ID && vis_any_probe(vis, vsize, id & ID_MASK) == 1;
+        seeded += __popcll(__ballot(ins));
+    }
+    return seeded;
+}
+
+// ---------------------------------------------------------------------------
+// LDS-resident sorted list: the query search's layer 0 past the widest
+// register list (512 < max(ef, k) <= LL_MAX_EF; option beam_lds_min_ef lowers
+// the threshold).  The same list as BList -- entry i holds (d, id | EXP_BIT),
+// ordered by (d, id), +inf / EMPTY_ID when empty -- with the same operations
+// (bl_init / bl_at / bl_insert / bl_next / bl_merge / bl_seed), so beam_layer
+// runs the same search on either.  All fields are wave-uniform.
+//   n  : the filled entries, [0, n); the rest of [0, cap) is empty
+//   nx : every entry below nx is expanded (bl_next scans from there)
+// ---------------------------------------------------------------------------
+constexpr int LL_MAX_EF = 2048;
+struct LList {
+    float* d;     // [cap] distances (LDS)
+    uint32_t* i;  // [cap] ids
+    float* cb;    // [128] the step's candidate buffer (bl_cbuf)
+    int cap;      // a multiple of 64, >= ef
+    int n, nx;
+};
+// the list's LDS words for max(ef, k) = efl: distances, ids, candidate buffer
+__host__ __device__ inline int ll_cap(int efl) { return (efl + 63) & ~63; }
+__host__ __device__ inline int ll_words(int efl) { return 2 * ll_cap(efl) + 128; }
+__device__ __forceinline__ void ll_place(LList& L, uint32_t* mem, int efl) {
+    L.cap = ll_cap(efl);
+    L.cb = reinterpret_cast<float*>(mem);
+    L.d = reinterpret_cast<float*>(mem + 128);
+    L.i = mem + 128 + L.cap;
+    L.n = L.nx = 0;
+}
+
+__device__ __forceinline__ float* bl_cbuf(LList& L, float*) { return L.cb; }
+
+__device__ __forceinline__ void bl_init(LList& L) {
+    for (int t = lane_id(); t < L.cap; t += 64) {
+        L.d[t] = __int_as_float(0x7f800000);
+        L.i[t] = EMPTY_ID;
+    }
+    L.n = L.nx = 0;
+    wave_sync();
+}
+
+__device__ __forceinline__ void bl_at(const LList& L, int idx, float& d, uint32_t& id) {
+    d = __int_as_float(uni(__float_as_int(L.d[idx])));
+    id = uni(L.i[idx]);
+}
+
+// bl_insert's semantics (the best ef of the list and everything offered; NaN,
+// a row already listed and anything no better than a full list's worst entry
+// are dropped); entries [pos, n) move up by one, highest 64-entry chunk first.
+__device__ __forceinline__ bool bl_insert(LList& L, int ef, float d, uint32_t u) {
+    if (!(d == d)) return false;  // NaN never enters the list
+    const int lane = lane_id();
+    const int n = L.n;
+    float wd;
+    uint32_t wi;
+    bl_at(L, ef - 1, wd, wi);
+    if (!lt_di(d, u, wd, wi & ID_MASK)) return false;
+    bool dup = false;
+    int pos = 0;
+    for (int b = 0; b < n; b += 64) {
+        const int idx = b + lane;
+        const bool in = idx < n;
+        const float ed = in ? L.d[idx] : 0.f;
+        const uint32_t ei = in ? L.i[idx] & ID_MASK : 0u;
+        dup |= in && ei == u;
+        pos += __popcll(__ballot(in && lt_di(ed, ei, d, u)));
+    }
+    if (__ballot(dup)) return false;
+    for (int c = (n - 1) >> 6; c >= 0 && c * 64 + 63 >= pos; --c) {
+        const int idx = c * 64 + lane;
+        const bool mv = idx >= pos && idx < n && idx + 1 < ef;
+        const float ed = mv ? L.d[idx] : 0.f;
+        const uint32_t ei = mv ? L.i[idx] : 0u;
+        wave_sync();  // (the chunk is read before its first entries are overwritten)
+        if (mv) {
+            L.d[idx + 1] = ed;
+            L.i[idx + 1] = ei;
+        }
+        wave_sync();
+    }
+    if (lane == 0) {  // pos <= n, and pos < ef where the list is full (d beat its worst)
+        L.d[pos] = d;
+        L.i[pos] = u;
+    }
+    wave_sync();
+    L.n = min(n + 1, ef);
+    if (pos <= L.nx) L.nx = pos;
+    return true;
+}
+
+// pick the first unexpanded entry, mark it expanded; returns EMPTY_ID if none
+__device__ __forceinline__ uint32_t bl_next(LList& L) {
+    const int lane = lane_id();
+    for (int b = L.nx & ~63; b < L.n; b += 64) {
+        const int idx = b + lane;
+        const bool in = idx >= L.nx && idx < L.n;
+        const uint32_t w = in ? L.i[idx] : EXP_BIT;
+        const unsigned long long m = __ballot((w & EXP_BIT) == 0);
+        if (m) {
+            const int l = __ffsll((long long)m) - 1;
+            const uint32_t id = rl_u(w, l);
+            if (lane == l) L.i[idx] = w | EXP_BIT;
+            wave_sync();
+            L.nx = b + l + 1;
+            return id;
+        }
+    }
+    L.nx = L.n;
+    return EMPTY_ID;
+}
+
+// bl_merge over the LDS list: the k <= 64 candidates of L.cb, each ranked among
+// the candidates and (binary search over L.d[0, ef], which can reach ef: see
+// bl_merge) in the list.  The list's entries move up in place by the number of
+// candidates placed at or before them (at most k <= 64 places), in 64-entry
+// chunks from the tail down to the lowest insertion point: a chunk is read
+// whole into registers before it is written, its writes go to indices at or
+// above their sources, and every chunk above it has been read already, so
+// nothing unread is overwritten and no second copy of the list is needed.
+// The candidates are written last, into the places the shift left.
+// An infinite distance, two equal candidate distances, a candidate equal to a
+// listed distance and a candidate past every listed entry (lb >= ef) send the
+// buffer through bl_insert, one candidate at a time.
+__device__ __forceinline__ void bl_merge(LList& L, int ef, int k, float*) {
+    const int lane = lane_id();
+    const float INF = __int_as_float(0x7f800000);
+    wave_sync();  // (the buffer was written by lane 0)
+    const float bd = lane < k ? L.cb[lane] : INF;
+    const uint32_t bi = lane < k ? reinterpret_cast<const uint32_t*>(L.cb)[64 + lane] : EMPTY_ID;
+    bool slow = __ballot(lane < k && !(bd < INF)) != 0;
+    int rk = 0;  // lane j < k: the candidates below candidate j
+    int lb = 0;  // lane j < k: the list entries (of the first ef) below candidate j
+    if (!slow) {
+        int eq = 0;
+        for (int j = 0; j < k; ++j) {
+            const float dj = rl_f(bd, j);
+            rk += dj < bd ? 1 : 0;
+            eq += dj == bd ? 1 : 0;
+        }
+        slow = __ballot(lane < k && eq > 1) != 0;
+    }
+    if (!slow) {
+        if (lane < k) {
+            // (the steps add up to 2 LL_MAX_EF - 1 >= ef, so lb can reach ef)
+#pragma unroll
+            for (int step = LL_MAX_EF; step >= 1; step >>= 1) {
+                const int t = lb + step - 1;
+                if (t < ef && L.d[t] < bd) lb += step;
+            }
+        }
+        slow = __ballot(lane < k && (lb >= ef || L.d[lb < ef ? lb : 0] == bd)) != 0;
+    }
+    if (slow) {
+        for (int j = 0; j < k; ++j) bl_insert(L, ef, rl_f(bd, j), rl_u(bi, j));
+        return;
+    }
+    // the distances are distinct: the best candidate has the lowest insertion
+    // point (and the lowest new place), the worst the highest
+    const int n = L.n;
+    const int minlb = rl_i(lb, __ffsll((long long)__ballot(lane < k && rk == 0)) - 1);
+    const int maxlb = rl_i(lb, __ffsll((long long)__ballot(lane < k && rk == k - 1)) - 1);
+    for (int c = (n - 1) >> 6; c >= (minlb >> 6); --c) {
+        const int idx = c * 64 + lane;
+        const bool in = idx >= minlb && idx < n;
+        const float ed = in ? L.d[idx] : 0.f;
+        const uint32_t ei = in ? L.i[idx] : 0u;
+        int sh = k;  // the candidates placed at or before entry idx
+        if (c * 64 < maxlb) {
+            sh = 0;
+            for (int j = 0; j < k; ++j) sh += idx >= rl_i(lb, j) ? 1 : 0;
+        }
+        wave_sync();
+        if (in && idx + sh < ef) {
+            L.d[idx + sh] = ed;
+            L.i[idx + sh] = ei;
+        }
+        wave_sync();
+    }
+    const int pos = rk + lb;
+    if (lane < k && pos < ef) {
+        L.d[pos] = bd;
+        L.i[pos] = bi;
+    }
+    wave_sync();
+    // the lowest unexpanded entry moved up with the candidates placed at or
+    // before it, unless a candidate (unexpanded) landed below it
+    const int up = __popcll(__ballot(lane < k && lb <= L.nx));
+    L.nx = min(L.nx + up, minlb);
+    L.n = min(n + k, ef);
+}
+
+__device__ __forceinline__ int bl_seed(const LList& L, uint32_t* vis, int vsize) {
+    int seeded = 0;
+    for (int b = 0; b < L.n; b += 64) {
+        const int idx = b + lane_id();
+        const bool ins = idx < L.n && vis_any_probe(vis, vsize, L.i[idx] & ID_MASK) == 1;
+        seeded += __popcll(__ballot(ins));
+    }
+    return seeded;
+}
+
 // How beam_layer scores one batch of new candidates (ids in lanes 0..cnt-1 of
 // cid) and hands the survivors to its sink: WaveBatch does it on the calling
 // wave; the multi-wave single-query kernel (beam.hpp MwBatch) spreads the rows
@@ -435,11 +657,11 @@ struct WaveBatch {
 // MERGE (the query search's layer 0 at ef > 128): the step's candidates go
 // through bl_merge once per step, with `mrg` (BL_MERGE_WORDS of LDS) as its
 // scratch.
-template <class C, int R, int G, bool COH = false, bool SCREEN = false, int XW = 1, bool MERGE = false,
-          class BEv = WaveBatch>
-__device__ __forceinline__ void beam_layer(const GraphDev& g, int layer, uint32_t entry, int ef, const QReg<C>& q, float qn,
-                           BList<R>& L, uint32_t* vis, int vsize, WaveStats& st, const BEv& bev = BEv(),
-                           float* mrg = nullptr) {
+// LT: the list, BList<R> (registers) or LList (LDS).
+template <class C, class LT, int G, bool COH, bool SCREEN, int XW, bool MERGE, class BEv>
+__device__ __forceinline__ void beam_layer_l(const GraphDev& g, int layer, uint32_t entry, int ef, const QReg<C>& q,
+                                             float qn, LT& L, uint32_t* vis, int vsize, WaveStats& st, const BEv& bev,
+                                             float* mrg) {
     const int lane = lane_id();
     bl_init(L);
     if (entry == EMPTY_ID) return;
@@ -551,11 +773,12 @@ __device__ __forceinline__ void beam_layer(const GraphDev& g, int layer, uint32_
                         bl_merge(L, ef, bk, mrg);
                         bk = 0;
                     }
+                    float* cb = bl_cbuf(L, mrg);
                     auto sink = [&](float d, uint32_t u) {
                         if (lt_di(d, u, wd, wi & ID_MASK)) {
                             if (lane == 0) {
-                                mrg[512 + bk] = d;
-                                reinterpret_cast<uint32_t*>(mrg)[576 + bk] = u;
+                                cb[bk] = d;
+                                reinterpret_cast<uint32_t*>(cb)[64 + bk] = u;
                             }
                             ++bk;
                         }
@@ -589,20 +812,19 @@ __device__ __forceinline__ void beam_layer(const GraphDev& g, int layer, uint32_
             wave_sync();
             vis_any_clear(vis, vsize);
             wave_sync();
-            // the list's members stay visited: they are the neighbourhood the
-            // next expansions keep meeting (fewer re-evaluations)
-            int seeded = 0;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const uint32_t id = L.i[r];
-                const bool ins = id != EMPTY_ID && vis_any_probe(vis, vsize, id & ID_MASK) == 1;
-                seeded += __popcll(__ballot(ins));
-            }
+            vcount = bl_seed(L, vis, vsize);  // the list's members stay visited
             wave_sync();
-            vcount = seeded;
             st.resets += 1;
         }
     }
+}
+
+template <class C, int R, int G, bool COH = false, bool SCREEN = false, int XW = 1, bool MERGE = false,
+          class BEv = WaveBatch>
+__device__ __forceinline__ void beam_layer(const GraphDev& g, int layer, uint32_t entry, int ef, const QReg<C>& q, float qn,
+                           BList<R>& L, uint32_t* vis, int vsize, WaveStats& st, const BEv& bev = BEv(),
+                           float* mrg = nullptr) {
+    beam_layer_l<C, BList<R>, G, COH, SCREEN, XW, MERGE, BEv>(g, layer, entry, ef, q, qn, L, vis, vsize, st, bev, mrg);
 }
 
 // ---------------------------------------------------------------------------

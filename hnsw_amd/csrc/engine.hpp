@@ -48,6 +48,7 @@ struct SearchArgs {
     int upper_ef;                 // beam: width of the upper-layer descent (1 = greedy, the reference's k = 1)
     int64_t mw_max_b;             // beam: batches up to this size run a workgroup per query (0 = never)
     int expand = 1;               // beam: entries expanded per layer-0 step (1, 2 or 4; beam_layer XW)
+    int lds_min_ef = 513;         // beam: the smallest max(ef, k) whose layer-0 list lives in LDS (k_search_beam_lds)
 };
 
 // negative-example re-ranking epilogue (graph.go:1116-1537)

@@ -408,9 +408,20 @@ int search_body(mhnsw_index* h, const float* queries, bool on_device, int64_t B,
         a.mw_max_b = h->beam_mw_max_b;
         a.expand = h->search_expand;
         if (mode == MHNSW_MODE_BEAM) {
-            if (std::max(ef, k) > 512) return fail(h, MHNSW_EUNSUPPORTED, "beam mode supports max(ef,k) <= 512");
+            const int efl = std::max(ef, k);
+            if (efl > 2048) return fail(h, MHNSW_EUNSUPPORTED, "beam mode supports max(ef,k) <= 2048");
+            a.lds_min_ef = h->beam_lds_min_ef;
+            // the LDS-list tier re-seeds up to efl ids after a visited reset: an
+            // automatically sized 32-bit set holds at least 4 efl entries there (at
+            // 5,120, resetting at 3/4 full, ef 2048 would reset every few steps).  An
+            // explicit vis_entries is kept as given: the results do not depend on it.
+            if (efl >= a.lds_min_ef && !a.vis16 && h->vis_entries <= 0) a.vis_n = std::max(a.vis_n, 4 * efl);
             if (timing) HIPCHK(h, hipEventRecord(h->ev0, s));
-            LCHK(h, launch_search_beam(a, h->lpr, h->vpl, s));
+            int lr = launch_search_beam(a, h->lpr, h->vpl, s);
+            if (lr == -2)
+                return fail(h, MHNSW_EUNSUPPORTED, "beam search LDS budget exceeded (ef=%d, k=%d, vis_entries=%d)", ef, k,
+                            a.vis_n);
+            LCHK(h, lr);
             if (timing) HIPCHK(h, hipEventRecord(h->ev1, s));
         } else {
             if (timing) HIPCHK(h, hipEventRecord(h->ev0, s));

@@ -110,7 +110,11 @@ int mhnsw_seed(mhnsw_index *h, uint64_t seed); /* Rng = rand.New(rand.NewSource(
  * many queries run one workgroup of 4 waves per query -- the single-query
  * latency path of ParallelSearch, graph.go:631-790; default 512, 0 = never;
  * results are identical either way; the standard search only: search_expand 2 / 4
- * run the one-wave kernel), "build_mw_max" (batched insert with the screening
+ * run the one-wave kernel), "beam_lds_min_ef" (beam mode: the smallest max(ef, k)
+ * whose layer-0 list lives in LDS instead of registers; default 513, i.e. past
+ * the widest register list, valid [65, 513]; the results are identical on either
+ * list, lower values let the LDS list be run against the register lists at
+ * equal ef), "build_mw_max" (batched insert with the screening
  * copy, build_expand 2-4: a layer launch of at most this many inserts runs one
  * workgroup of 4 waves per insert, the candidate batches of its searches split
  * over the waves; default 256, 0 = never; the same graph either way), "vis_compact" (beam mode at max(ef, k) > 128 and batched insert at
@@ -176,7 +180,11 @@ int mhnsw_add_reached(const mhnsw_index *h, int64_t *reached);
 /* ---- Graph.Search / Graph.BatchSearch (graph.go:534-625, 1047-1110) ----
  * B queries of `dim` floats; outputs hold B*k slots; out_n[b] results for
  * query b.  ef <= 0 uses EfSearch.  entry_key (nullable) replaces the
- * arbitrary layer.entry() (graph.go:250-258) of the top layer. */
+ * arbitrary layer.entry() (graph.go:250-258) of the top layer.
+ * MHNSW_MODE_BEAM takes 1 <= max(ef, k) <= 2048 (up to 512 the list is held in
+ * registers, from 513 in LDS: the same search, bit-identical to the oracle's);
+ * past 2048 the call fails with MHNSW_EUNSUPPORTED, "beam mode supports
+ * max(ef,k) <= 2048". */
 int mhnsw_search(mhnsw_index *h, const float *queries, int64_t B, int dim, int k, int mode, int ef,
                  const int64_t *entry_key, int64_t *out_keys, float *out_dist, int32_t *out_n);
 int mhnsw_search_device(mhnsw_index *h, const float *d_queries, int64_t B, int dim, int k, int mode, int ef,
