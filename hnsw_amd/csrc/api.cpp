@@ -1084,6 +1084,9 @@ void mhnsw_destroy(mhnsw_index* h) {
     F(h->okeys.p);
     F(h->odist.p);
     F(h->on.p);
+    F(h->ordkey.p);
+    F(h->ordval.p);
+    F(h->ordtmp.p);
     F(h->nq.p);
     F(h->nneg.p);
     F(h->ncd.p);
@@ -1190,6 +1193,21 @@ int mhnsw_set_option(mhnsw_index* h, const char* name, int64_t v) {
     } else if (n == "search_expand") {
         if (v != 1 && v != 2 && v != 4) return fail(h, MHNSW_EINVAL, "search_expand must be 1, 2 or 4");
         h->search_expand = (int)v;
+    } else if (n == "search_order") {
+        if (v != 0 && v != 1) return fail(h, MHNSW_EINVAL, "search_order must be 0 or 1");
+        h->search_order = (int)v;
+    } else if (n == "search_order_min_b") {
+        if (v < 1) return fail(h, MHNSW_EINVAL, "search_order_min_b must be >= 1");
+        h->search_order_min_b = v;
+    } else if (n == "search_order_top") {
+        if (v < 0 || v >= MH_MAXL) return fail(h, MHNSW_EINVAL, "search_order_top must be in [0, %d]", MH_MAXL - 1);
+        h->search_order_top = (int)v;
+    } else if (n == "search_order_fields") {
+        if (v < 0 || v > 8) return fail(h, MHNSW_EINVAL, "search_order_fields must be in [0, 8]");
+        h->search_order_fields = (int)v;
+    } else if (n == "search_order_map") {
+        if (v != 0 && v != 1) return fail(h, MHNSW_EINVAL, "search_order_map must be 0 or 1");
+        h->search_order_map = (int)v;
     } else if (n == "prune_alpha_pct") {
         if (v < 50 || v > 400) return fail(h, MHNSW_EINVAL, "prune_alpha_pct must be in [50, 400]");
         h->alpha_pct = (int)v;
@@ -1290,6 +1308,11 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
     else if (n == "keep_pruned") *v = h->keep_pruned;
     else if (n == "build_expand") *v = h->build_expand;
     else if (n == "search_expand") *v = h->search_expand;
+    else if (n == "search_order") *v = h->search_order;
+    else if (n == "search_order_min_b") *v = h->search_order_min_b;
+    else if (n == "search_order_top") *v = h->search_order_top;
+    else if (n == "search_order_fields") *v = h->search_order_fields;
+    else if (n == "search_order_map") *v = h->search_order_map;
     else if (n == "upper_efc") *v = h->upper_efc;
     else if (n == "prune_alpha_pct") *v = h->alpha_pct;
     else if (n == "batch_min") *v = h->batch_min;

@@ -38,29 +38,60 @@ int launch_beam_cfg(const SearchArgs& a, hipStream_t s);
 // the visited set's LDS words (the merge scratch follows it)
 __host__ __device__ inline int beam_vis_words(const SearchArgs& a) { return a.vis16 ? VIS16_WORDS : a.vis_n; }
 
-// the greedy descent (ef = upper_ef) from the top layer's entry to layer 0's
-template <class C, int G, bool SCREEN, class BEv>
+// The ordered path splits the descent: the pre-pass walks the layers of the sort
+// key and above, top .. beam_order_lo, and the layer-0 launch walks the rest
+// from where it stopped (the walks of the upper layers are what the queries of
+// a cell share; splitting below the key keeps the pre-pass short).
+__host__ __device__ inline int beam_order_lo(const SearchArgs& a) { return a.key_n > 0 ? a.key_top - a.key_n + 1 : 1; }
+
+// the greedy descent (ef = upper_ef) from node ep through the layers l_hi .. l_lo
+// (the whole descent: the top layer's entry, top .. 1); to0: down to layer 0's
+// entry.  KEY (the ordered path's pre-pass): *key collects the node the descent
+// stood on when it left each of the layers key_top .. key_top - key_n + 1, the
+// highest layer in the most significant bits.
+template <class C, int G, bool SCREEN, bool KEY = false, class BEv>
 __device__ __forceinline__ uint32_t beam_descend(const SearchArgs& a, const QReg<C>& q, float qn, uint32_t* smem,
-                                                 int vsz, WaveStats& st, const BEv& bev) {
-    uint32_t ep = a.entry;
+                                                 int vsz, WaveStats& st, const BEv& bev, uint32_t ep, int l_hi,
+                                                 int l_lo, bool to0, unsigned long long* key = nullptr) {
     {
         BList<1> L1;
-        for (int l = a.top; l >= 1; --l) {  // greedy descent, ef = 1
+        for (int l = l_hi; l >= l_lo; --l) {  // greedy descent, ef = 1
+            bool skip = false;
             if (a.g.layers[l].deg[ep] == -2) {  // not in this layer: restart at its entry
                 const int32_t e = a.layer_entry[l];
-                if (e < 0) continue;
-                ep = (uint32_t)e;
+                if (e < 0)
+                    skip = true;
+                else
+                    ep = (uint32_t)e;
             }
-            beam_layer<C, 1, G, false, SCREEN, 1>(a.g, l, ep, a.upper_ef, q, qn, L1, smem, vsz, st, bev);
-            float d;
-            uint32_t id;
-            bl_at(L1, 0, d, id);
-            if (id != EMPTY_ID) ep = id & ID_MASK;
+            if (!skip) {
+                beam_layer<C, 1, G, false, SCREEN, 1>(a.g, l, ep, a.upper_ef, q, qn, L1, smem, vsz, st, bev);
+                float d;
+                uint32_t id;
+                bl_at(L1, 0, d, id);
+                if (id != EMPTY_ID) ep = id & ID_MASK;
+            }
+            if constexpr (KEY) {  // (every query shifts the same number of fields in)
+                if (l <= a.key_top && l > a.key_top - a.key_n) {
+                    // a field narrower than an id holds a hash of it: two cells that collide are
+                    // merely sorted together
+                    const uint32_t f = a.key_hash ? (ep * 2654435761u) >> (32 - a.key_id_bits)
+                                                  : ep & ((1u << a.key_id_bits) - 1u);
+                    *key = (*key << a.key_id_bits) | (unsigned long long)f;
+                }
+            }
         }
     }
-    if (a.g.layers[0].deg[ep] == -2) ep = (uint32_t)a.layer_entry[0];
+    if (to0 && a.g.layers[0].deg[ep] == -2) ep = (uint32_t)a.layer_entry[0];
     return ep;
 }
+
+// where query b's descent in the layer-0 kernels starts: the top layer's entry,
+// or (ordered path) the node and the layer the pre-pass stopped above
+__device__ __forceinline__ uint32_t beam_entry_of(const SearchArgs& a, int64_t b) {
+    return a.order ? uni(a.ep0[b]) : a.entry;
+}
+__device__ __forceinline__ int beam_entry_layer(const SearchArgs& a) { return a.order ? beam_order_lo(a) - 1 : a.top; }
 
 // rows [nvalid, k) of query b's outputs: no result
 __device__ __forceinline__ void beam_pad_out(const SearchArgs& a, int64_t b, int nvalid) {
@@ -78,7 +109,8 @@ __device__ __forceinline__ void beam_query(const SearchArgs& a, int64_t b, const
                                            WaveStats& st, const BEv& bev) {
     const int lane = lane_id();
     const int vsz = a.vis16 ? -1 : a.vis_n;  // (beam_layer: < 0 selects the compact set)
-    const uint32_t ep = beam_descend<C, G, SCREEN>(a, q, qn, smem, vsz, st, bev);
+    const uint32_t ep = beam_descend<C, G, SCREEN>(a, q, qn, smem, vsz, st, bev, beam_entry_of(a, b),
+                                                   beam_entry_layer(a), 1, true);
     BList<R> L;
     const int efl = a.ef > a.k ? a.ef : a.k;
     // lists of 256 / 512 entries merge each step's candidates at once, with the
@@ -105,6 +137,19 @@ __device__ __forceinline__ void beam_query(const SearchArgs& a, int64_t b, const
         nvalid += __popcll(m);
     }
     beam_pad_out(a, b, min(nvalid, a.k));
+}
+
+// The query of workgroup i.  Fused path: query i.  Ordered path: the query at
+// sorted position i, or with order_chunk at position (i % 8) * chunk + i / 8:
+// workgroups i and i + 8 have been observed to share an XCD, so each XCD then
+// walks one contiguous run of the sorted queries (speed only: any mapping that
+// covers every position once is correct).  -1: nothing to do.
+__device__ __forceinline__ int64_t beam_query_of(const SearchArgs& a, int64_t i) {
+    if (!a.order) return i < a.B ? i : -1;
+    const int64_t pos = a.order_chunk > 0 ? (i & 7) * a.order_chunk + (i >> 3) : i;
+    if (pos >= a.B || (a.order_chunk > 0 && (i >> 3) >= a.order_chunk)) return -1;
+    const uint32_t b = uni(a.order[pos]);
+    return b < (uint64_t)a.B ? (int64_t)b : -1;
 }
 
 __device__ __forceinline__ void beam_stats(const SearchArgs& a, const WaveStats& st) {
@@ -137,8 +182,8 @@ template <class C, int R, int G, bool SCREEN, int XW>
 __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_eu(R >= 8 ? MH_BEAM_WIDE_WAVES : 2)))
 void k_search_beam(SearchArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    const int64_t b = blockIdx.x;
-    if (b >= a.B) return;
+    const int64_t b = beam_query_of(a, blockIdx.x);
+    if (b < 0) return;
     QReg<C> q;
     load_query(q, a.q + (size_t)b * C::PITCH);
     const float qn = query_norm(q);
@@ -191,13 +236,41 @@ __global__ __launch_bounds__(64 * BMW_WAVES) void k_search_beam_mw(SearchArgs a)
     beam_stats(a, st);
 }
 
+// ---------------------------------------------------------------------------
+// ordered path, pre-pass: the descent through the layers top .. beam_order_lo
+// alone, one wave per query, with the fused kernels' upper_ef, visited set and
+// screen.  Writes the node it stopped on, the sort key of the descent path and
+// the sort's value (the query's index); its counters go into the same slots as
+// the layer-0 launch's, which walks the remaining layers.
+// ---------------------------------------------------------------------------
+template <class C, int G, bool SCREEN>
+__global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_beam_descend(SearchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const int64_t b = blockIdx.x;
+    if (b >= a.B) return;
+    QReg<C> q;
+    load_query(q, a.q + (size_t)b * C::PITCH);
+    const float qn = query_norm(q);
+    WaveStats st;
+    const int vsz = a.vis16 ? -1 : a.vis_n;
+    unsigned long long key = 0;
+    const uint32_t ep =
+        beam_descend<C, G, SCREEN, true>(a, q, qn, smem, vsz, st, WaveBatch(), a.entry, a.top, beam_order_lo(a), false, &key);
+    if (lane_id() == 0) {
+        a.ep0[b] = ep;
+        a.okey[b] = key;
+        a.oidx[b] = (uint32_t)b;
+    }
+    beam_stats(a, st);
+}
+
 template <class C, int R, int G, int XW>
 static int launch_beam_t(const SearchArgs& a, hipStream_t s) {
     const size_t lds = (size_t)4 * (size_t)(R >= 4 ? std::max(a.vis_n, beam_vis_words(a) + BL_MERGE_WORDS) : a.vis_n);
     // small batch: a workgroup per query (the standard search only; a wider
     // expansion runs the one-wave kernel at every batch size)
     if constexpr (XW == 1) {
-        if (R <= 2 && a.B <= a.mw_max_b) {
+        if (R <= 2 && beam_small_batch(a) && !a.order) {
             if (a.g.h16)
                 hipLaunchKernelGGL((k_search_beam_mw<C, R, G, true>), dim3((unsigned)a.B), dim3(64 * BMW_WAVES), lds, s,
                                    a);
@@ -207,10 +280,11 @@ static int launch_beam_t(const SearchArgs& a, hipStream_t s) {
             return hipGetLastError() == hipSuccess ? 0 : -1;
         }
     }
+    const unsigned grid = (unsigned)(a.order ? beam_order_grid(a) : a.B);
     if (a.g.h16)
-        hipLaunchKernelGGL((k_search_beam<C, R, G, true, XW>), dim3((unsigned)a.B), dim3(64), lds, s, a);
+        hipLaunchKernelGGL((k_search_beam<C, R, G, true, XW>), dim3(grid), dim3(64), lds, s, a);
     else
-        hipLaunchKernelGGL((k_search_beam<C, R, G, false, XW>), dim3((unsigned)a.B), dim3(64), lds, s, a);
+        hipLaunchKernelGGL((k_search_beam<C, R, G, false, XW>), dim3(grid), dim3(64), lds, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -224,8 +298,8 @@ static int launch_beam_t(const SearchArgs& a, hipStream_t s) {
 template <class C, int G, bool SCREEN, int XW>
 __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_search_beam_lds(SearchArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    const int64_t b = blockIdx.x;
-    if (b >= a.B) return;
+    const int64_t b = beam_query_of(a, blockIdx.x);
+    if (b < 0) return;
     const int lane = lane_id();
     QReg<C> q;
     load_query(q, a.q + (size_t)b * C::PITCH);
@@ -233,7 +307,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_search_be
     WaveStats st;
     const WaveBatch bev;
     const int vsz = a.vis16 ? -1 : a.vis_n;
-    const uint32_t ep = beam_descend<C, G, SCREEN>(a, q, qn, smem, vsz, st, bev);
+    const uint32_t ep = beam_descend<C, G, SCREEN>(a, q, qn, smem, vsz, st, bev, beam_entry_of(a, b),
+                                                   beam_entry_layer(a), 1, true);
     const int efl = a.ef > a.k ? a.ef : a.k;
     LList L;
     ll_place(L, smem + ((beam_vis_words(a) + 3) & ~3), efl);
@@ -274,10 +349,11 @@ static int launch_beam_lds_t(const SearchArgs& a, hipStream_t s) {
     if (efl > LL_MAX_EF) return -4;
     const size_t lds = beam_lds_bytes(a);
     if (lds > BEAM_LDS_MAX_BYTES) return -2;
+    const unsigned grid = (unsigned)(a.order ? beam_order_grid(a) : a.B);
     if (a.g.h16)
-        hipLaunchKernelGGL((k_search_beam_lds<C, G, true, XW>), dim3((unsigned)a.B), dim3(64), lds, s, a);
+        hipLaunchKernelGGL((k_search_beam_lds<C, G, true, XW>), dim3(grid), dim3(64), lds, s, a);
     else
-        hipLaunchKernelGGL((k_search_beam_lds<C, G, false, XW>), dim3((unsigned)a.B), dim3(64), lds, s, a);
+        hipLaunchKernelGGL((k_search_beam_lds<C, G, false, XW>), dim3(grid), dim3(64), lds, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -307,6 +383,28 @@ int launch_beam_cfg(const SearchArgs& a, hipStream_t s) {
 template <int L, int V, int XW>
 int launch_beam_lds_cfg(const SearchArgs& a, hipStream_t s) {
     return launch_beam_lds_t<Cfg<L, V>, beam_group<L, V>(), XW>(a, s);
+}
+
+// the ordered path's pre-pass (k_beam_descend), instantiated in beam_desc.hip.
+// The same failures as the layer-0 launch it precedes: -4 past the LDS list's
+// capacity, -2 when the visited set and the list do not fit a workgroup's LDS.
+template <int L, int V>
+int launch_beam_descend_cfg(const SearchArgs& a, hipStream_t s) {
+    using C = Cfg<L, V>;
+    constexpr int G = beam_group<L, V>();
+    const int efl = a.ef > a.k ? a.ef : a.k;
+    if (efl >= a.lds_min_ef) {
+        if (efl > LL_MAX_EF) return -4;
+        if (beam_lds_bytes(a) > BEAM_LDS_MAX_BYTES) return -2;
+    } else if (efl > 512) {
+        return -4;
+    }
+    const size_t lds = (size_t)4 * (size_t)std::max(a.vis_n, beam_vis_words(a));
+    if (a.g.h16)
+        hipLaunchKernelGGL((k_beam_descend<C, G, true>), dim3((unsigned)a.B), dim3(64), lds, s, a);
+    else
+        hipLaunchKernelGGL((k_beam_descend<C, G, false>), dim3((unsigned)a.B), dim3(64), lds, s, a);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 }  // namespace mh

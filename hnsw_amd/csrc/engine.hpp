@@ -49,7 +49,29 @@ struct SearchArgs {
     int64_t mw_max_b;             // beam: batches up to this size run a workgroup per query (0 = never)
     int expand = 1;               // beam: entries expanded per layer-0 step (1, 2 or 4; beam_layer XW)
     int lds_min_ef = 513;         // beam: the smallest max(ef, k) whose layer-0 list lives in LDS (k_search_beam_lds)
+    // beam, ordered path (option "search_order"): the descent through the layers
+    // of the sort key and above runs as a pre-pass (k_beam_descend) that writes
+    // ep0 / okey / oidx; the keys are sorted into `order`, and the layer-0
+    // kernels take their query from it and finish its descent (nullptr: the
+    // fused path, workgroup b runs query b with its whole descent)
+    const uint32_t* order = nullptr;     // [B] sorted position -> query
+    uint32_t* ep0 = nullptr;             // [B] the node each query's pre-pass stopped on (beam.hpp beam_order_lo)
+    unsigned long long* okey = nullptr;  // [B] sort key: the descent's nodes of layers key_top .. key_top - key_n + 1
+    uint32_t* oidx = nullptr;            // [B] 0 .. B - 1 (the sort's values)
+    int key_top = 0, key_n = 0;          // the layers in the key (key_n = 0: every key is 0)
+    int key_id_bits = 1;                 // bits per field of the key (in [1, 31])
+    int key_hash = 0;                    // the fields are narrower than a node id: they hold a hash of it
+    int64_t order_chunk = 0;             // > 0: workgroup i takes position (i % 8) * chunk + i / 8; 0: position i
 };
+
+// the launch that runs one workgroup of 4 waves per query (beam.hpp
+// k_search_beam_mw): small batches of the standard search on the narrow lists
+inline bool beam_small_batch(const SearchArgs& a) {
+    const int efl = a.ef > a.k ? a.ef : a.k;
+    return a.expand != 2 && a.expand != 4 && efl <= 128 && efl < a.lds_min_ef && a.B <= a.mw_max_b;
+}
+// workgroups of an ordered layer-0 launch
+inline int64_t beam_order_grid(const SearchArgs& a) { return a.order_chunk > 0 ? 8 * a.order_chunk : a.B; }
 
 // negative-example re-ranking epilogue (graph.go:1116-1537)
 struct NegArgs {
@@ -80,6 +102,12 @@ int launch_sweep(const float* q, const float* X, int64_t n, int pitch, int lpr, 
                  hipStream_t s);
 int launch_sweep_raw(const float* q, const float* X, int64_t n, int dim, int metric, float* out, hipStream_t s);
 int launch_search_beam(const SearchArgs& a, int lpr, int vpl, hipStream_t s);
+// ordered path: the descent pre-pass (writes a.ep0 / a.okey / a.oidx, adds its
+// counters to a.stats), then the sort of the keys into the permutation (order.hip)
+int launch_beam_descend(const SearchArgs& a, int lpr, int vpl, hipStream_t s);
+int order_sort_temp_bytes(int64_t n, size_t* bytes);
+int launch_order_sort(const unsigned long long* keys, unsigned long long* keys_sorted, const uint32_t* idx,
+                      uint32_t* order, int64_t n, int key_bits, void* temp, size_t temp_bytes, hipStream_t s);
 int launch_search_compat(const SearchArgs& a, int lpr, int vpl, hipStream_t s);
 
 // ---- build ----

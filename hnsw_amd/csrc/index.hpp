@@ -29,6 +29,14 @@
 
 using namespace mh;
 
+// defaults of "search_order" / "search_order_min_b" (measured: DESIGN.md "Query order")
+#ifndef MH_SEARCH_ORDER_DEFAULT
+#define MH_SEARCH_ORDER_DEFAULT 1
+#endif
+#ifndef MH_SEARCH_ORDER_MIN_B_DEFAULT
+#define MH_SEARCH_ORDER_MIN_B_DEFAULT 16384
+#endif
+
 namespace mhh {
 
 template <class T>
@@ -82,6 +90,14 @@ struct mhnsw_index {
     int upper_ef = 1;         // beam search: upper-layer descent width
     int64_t beam_mw_max_b = 512;  // beam search: batches up to this size run one workgroup of 4 waves per query
     int beam_lds_min_ef = 513;    // beam search: the smallest max(ef, k) whose layer-0 list lives in LDS ([65, 513])
+    // beam search, ordered path: batches of at least search_order_min_b queries (the one-wave
+    // kernels only) run the descent as a pre-pass, sort the queries by descent path and search
+    // layer 0 in that order (DESIGN.md "Query order"); the same results either way
+    int search_order = MH_SEARCH_ORDER_DEFAULT;
+    int64_t search_order_min_b = MH_SEARCH_ORDER_MIN_B_DEFAULT;
+    int search_order_top = 0;     // highest layer in the sort key (0 = by batch size, search_host.cpp order_key_top)
+    int search_order_fields = 0;  // layers in the sort key (0 = search_host.cpp ORDER_KEY_FIELDS)
+    int search_order_map = 0;    // 0: XCD-contiguous chunks of the sorted queries, 1: workgroup i takes position i
     int64_t build_mw_max = 256;  // batched insert: launches of at most this many inserts run 4 waves per insert
     int screen = 1;           // beam search / batched insert fp16 screening copy (results unchanged)
     int fuse_descent = 1;     // batched insert: all greedy descents of a batch in one launch (same graph)
@@ -140,6 +156,10 @@ struct mhnsw_index {
     DevBuf<int64_t> okeys;
     DevBuf<float> odist;
     DevBuf<int32_t> on;
+    // ordered beam search: sort keys in / out [2 B], {query index, order, layer-0 entry} [3 B], sort scratch
+    DevBuf<unsigned long long> ordkey;
+    DevBuf<uint32_t> ordval;
+    DevBuf<uint8_t> ordtmp;
     DevBuf<float> nq, nneg, ncd;  // negatives: queries, padded negative rows, candidate distances
     DevBuf<int64_t> nck, nok;
     DevBuf<int32_t> ncn, nci, noff, non;

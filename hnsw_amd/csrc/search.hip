@@ -17,6 +17,7 @@ namespace mh {
     extern template int launch_beam_lds_cfg<L, V, 1>(const SearchArgs&, hipStream_t); \
     extern template int launch_beam_lds_cfg<L, V, 2>(const SearchArgs&, hipStream_t); \
     extern template int launch_beam_lds_cfg<L, V, 4>(const SearchArgs&, hipStream_t); \
+    extern template int launch_beam_descend_cfg<L, V>(const SearchArgs&, hipStream_t); \
     extern template int launch_compat_cfg<L, V>(const SearchArgs&, hipStream_t);     \
     extern template int launch_negatives_cfg<L, V>(const NegArgs&, hipStream_t);
 MH_FOR_EACH_CFG(X_)
@@ -430,6 +431,15 @@ int launch_search_beam(const SearchArgs& a, int lpr, int vpl, hipStream_t s) {
         return a.expand == 4 ? launch_beam_cfg<L, V, 4>(a, s)         \
                : a.expand == 2 ? launch_beam_cfg<L, V, 2>(a, s)       \
                                : launch_beam_cfg<L, V, 1>(a, s);
+    MH_FOR_EACH_CFG(X_)
+#undef X_
+    return -3;
+}
+
+int launch_beam_descend(const SearchArgs& a, int lpr, int vpl, hipStream_t s) {
+    if (a.B <= 0) return 0;
+#define X_(L, V, G) \
+    if (lpr == L && vpl == V) return launch_beam_descend_cfg<L, V>(a, s);
     MH_FOR_EACH_CFG(X_)
 #undef X_
     return -3;

@@ -29,6 +29,31 @@ int search_body(mhnsw_index* h, const float* queries, bool on_device, int64_t B,
                 const int64_t* entry_key, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool timing,
                 int32_t* out_ids, bool sticky);
 
+// The ordered beam search's sort key: the node the descent stood on when it left
+// layer key_top in the most significant field, then the nodes of the
+// ORDER_KEY_FIELDS - 1 layers below it (option search_order_fields), each in
+// 64 / fields bits: the node id where it fits, else a hash of it.  The sort is
+// then a walk of the descent tree: the queries of one cell of the lowest field
+// are contiguous, and so are the cells under one parent.  key_top (option
+// search_order_top, 0 = automatic): the lowest layer with at most
+// B / ORDER_CELL_QUERIES nodes (measured, DESIGN.md "Query order").  A graph
+// whose only layer is 0 has no field: every key is 0.
+constexpr int ORDER_KEY_FIELDS = 3;
+constexpr int64_t ORDER_CELL_QUERIES = 128;
+void order_key_layers(const mhnsw_index* h, int64_t B, int top, SearchArgs& a) {
+    int bits = 1;
+    while (bits < 31 && (int64_t(1) << bits) < h->capn) ++bits;
+    int kt = h->search_order_top;
+    if (kt <= 0) {
+        kt = 1;
+        while (kt < top && h->layers[kt].count > std::max<int64_t>(1, B / ORDER_CELL_QUERIES)) ++kt;
+    }
+    a.key_top = std::min(kt, top);
+    a.key_n = std::min(h->search_order_fields > 0 ? h->search_order_fields : ORDER_KEY_FIELDS, a.key_top);
+    a.key_id_bits = a.key_n > 0 ? std::min(bits, 64 / a.key_n) : 1;
+    a.key_hash = a.key_id_bits < bits;
+}
+
 // every search: order after the previous scratch user (another stream), and
 // after the metadata copies this call makes on the handle's stream.  sticky:
 // the kernels report into d_err[1] (an asynchronous *_device search the caller
@@ -416,8 +441,29 @@ int search_body(mhnsw_index* h, const float* queries, bool on_device, int64_t B,
             // 5,120, resetting at 3/4 full, ef 2048 would reset every few steps).  An
             // explicit vis_entries is kept as given: the results do not depend on it.
             if (efl >= a.lds_min_ef && !a.vis16 && h->vis_entries <= 0) a.vis_n = std::max(a.vis_n, 4 * efl);
+            // ordered path: the descent as a pre-pass, the queries sorted by descent
+            // path, layer 0 searched in that order (the one-wave kernels only)
+            const bool ordered = h->search_order && B >= h->search_order_min_b && !beam_small_batch(a);
+            size_t tmp_bytes = 0;
+            if (ordered) {
+                LCHK(h, order_sort_temp_bytes(B, &tmp_bytes));
+                if ((r = ensure_buf(h, h->ordkey, (size_t)2 * B)) || (r = ensure_buf(h, h->ordval, (size_t)3 * B)) ||
+                    (r = ensure_buf(h, h->ordtmp, std::max<size_t>(tmp_bytes, 1))))
+                    return r;
+                a.okey = h->ordkey.p;
+                a.oidx = h->ordval.p;
+                a.ep0 = h->ordval.p + 2 * B;
+                order_key_layers(h, B, top, a);
+                a.order_chunk = h->search_order_map == 0 ? (B + 7) / 8 : 0;
+            }
             if (timing) HIPCHK(h, hipEventRecord(h->ev0, s));
-            int lr = launch_search_beam(a, h->lpr, h->vpl, s);
+            int lr = 0;
+            if (ordered && !(lr = launch_beam_descend(a, h->lpr, h->vpl, s))) {
+                LCHK(h, launch_order_sort(h->ordkey.p, h->ordkey.p + B, h->ordval.p, h->ordval.p + B, B,
+                                          a.key_n * a.key_id_bits, h->ordtmp.p, tmp_bytes, s));
+                a.order = h->ordval.p + B;
+            }
+            if (!lr) lr = launch_search_beam(a, h->lpr, h->vpl, s);
             if (lr == -2)
                 return fail(h, MHNSW_EUNSUPPORTED, "beam search LDS budget exceeded (ef=%d, k=%d, vis_entries=%d)", ef, k,
                             a.vis_n);

@@ -90,7 +90,26 @@ int mhnsw_seed(mhnsw_index *h, uint64_t seed); /* Rng = rand.New(rand.NewSource(
  * together, their adjacency rows fetched in one round trip and their new
  * neighbours scored as one batch; a different search from 1 (results can
  * differ), bit-identical to the oracle's og_set_search_expand; always the
- * one-wave kernel), "exact_kk",
+ * one-wave kernel), "search_order" (beam mode, 0 or 1: batches of at least
+ * "search_order_min_b" queries run the greedy descent as a pre-pass, sort the
+ * queries by their descent path and search layer 0 in that order, so that
+ * queries walking the same neighbourhood run on one XCD at the same time and
+ * share its L2; each query's search is independent of the others, so the
+ * lists and the search counters are the same bit for bit; smaller batches and
+ * the 4-wave small-batch kernel always run the single fused launch; the
+ * pre-pass, the sort and the search all run on the caller's stream from
+ * buffers the handle owns, and last_kernel_ms covers all of them),
+ * "search_order_min_b" (>= 1: the smallest ordered batch; the default is the
+ * smallest measured batch at which the extra launches do not cost more than
+ * the order saves), "search_order_top" (the highest layer whose descent node
+ * goes into the sort key, 0 (default) = the lowest layer with at most
+ * batch / 128 nodes), "search_order_fields" (how many layers from there down
+ * go into the key, 1-8, 0 (default) = 3; each takes 64 / fields bits, a hash
+ * of the node id where the id does not fit; the pre-pass stops at the key's
+ * lowest layer and the search launch walks the layers below it),
+ * "search_order_map" (0 (default): workgroup i takes sorted position
+ * (i % 8) * ceil(B / 8) + i / 8, one contiguous run of the sorted queries per
+ * XCD; 1: workgroup i takes position i), "exact_kk",
  * "exact_thr_rank" (precision 3: the threshold is the sample's J-th best score,
  * J = max(k, this) capped at kk; 0 (default) = max(k, kk / 8)),
  * "exact_sample" (precision 3: at most this many row tiles form the threshold
