@@ -1,42 +1,73 @@
-// beam.hpp -- the batched beam search kernel (k_search_beam) and the
-// dimension-configuration list, shared by search.hip (dispatch) and the
-// beam_*.hip translation units that instantiate it per configuration (split
-// so that the kernel's 4 list widths x 2 screen modes x 10 configurations
-// compile in parallel).  Past the register lists (max(ef, k) > 512) the same
-// search runs on a list held in LDS: k_search_beam_lds, instantiated per
-// configuration, screen mode and XW in beam_w*.hip.
+// beam.hpp -- the batched beam search kernels and their launchers, shared by
+// search.hip (dispatch) and beam_units.hip, which instantiates them per
+// configuration in its units (split so that the 4 list widths x 2 screen
+// modes x 10 configurations compile in parallel).  One body, beam_query, runs
+// a query over either list: BList<R> in registers (k_search_beam,
+// k_search_beam_mw), or past them (max(ef, k) > 512) LList in LDS
+// (k_search_beam_lds).
 #pragma once
+#include <type_traits>
+
 #include "device_search.hpp"
 #include "engine.hpp"
 
 namespace mh {
 
-// group width per configuration (rows in flight per wave step)
-#define MH_FOR_EACH_CFG(X)      \
-    X(16, 1, 2)                 \
-    X(32, 1, 4)                 \
-    X(64, 1, 8)                 \
-    X(64, 2, 8)                 \
-    X(64, 3, 8)                 \
-    X(64, 4, 4)                 \
-    X(64, 6, 4)                 \
-    X(64, 8, 2)            \
-    X(64, 12, 1)           \
-    X(64, 16, 1)
-
 // XW: entries expanded per step of the layer-0 search (option "search_expand";
-// 1 = the standard best-first search).  XW 1 is instantiated in beam_a-d.hip,
-// XW 2 and 4 in beam_x2a/b.hip and beam_x4a/b.hip.
+// 1 = the standard best-first search).  The register lists' and the LDS list's
+// launchers are separate templates, so that beam_units.hip can instantiate the
+// two tiers in different objects.
 template <int L, int V, int XW>
 int launch_beam_cfg(const SearchArgs& a, hipStream_t s);
+template <int L, int V, int XW>
+int launch_beam_lds_cfg(const SearchArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // batched search: one wave per query
 // ---------------------------------------------------------------------------
-// One query b: greedy descent, the layer-0 beam, and its first k live entries
-// into the outputs.  BEv scores each batch of candidates (beam_layer).
-// the visited set's LDS words (the merge scratch follows it)
+// the width of the layer-0 list
+__host__ __device__ inline int beam_efl(const SearchArgs& a) { return a.ef > a.k ? a.ef : a.k; }
+// the tier: the LDS-resident list from max(ef, k) = lds_min_ef (513 unless the
+// option beam_lds_min_ef lowers it: past the widest register list)
+inline bool beam_in_lds(const SearchArgs& a) { return beam_efl(a) >= a.lds_min_ef; }
+
+// the visited set's LDS words (the list's part follows it)
 __host__ __device__ inline int beam_vis_words(const SearchArgs& a) { return a.vis16 ? VIS16_WORDS : a.vis_n; }
+
+// The dynamic LDS of a layer-0 launch over list LT, in 32-bit words: the
+// kernel places the list's part at `list` (bl_place), the launcher asks for
+// `words`.  Registers: bl_merge's scratch where the steps merge, and never
+// less than the vis_n words of the 32-bit set, which the compact set leaves
+// partly unused (the default compact set with the scratch fits the 20 KiB a
+// 2-wave SIMD allows).  The host sets vis16 only with vis_n >= VIS16_WORDS
+// (search_host.cpp), so for the lists that do not merge, and for the pre-pass,
+// this is vis_n itself.  LDS: the list, 16-byte aligned.
+struct BeamLds {
+    int list, words;
+};
+template <class LT>
+__host__ __device__ inline BeamLds beam_lds(const SearchArgs& a) {
+    const int vis = beam_vis_words(a);
+    if constexpr (bl_regs<LT> == 0) {
+        const int at = (vis + 3) & ~3;
+        return {at, at + ll_words(beam_efl(a))};
+    } else {
+        const int w = vis + (bl_merges<LT> ? BL_MERGE_WORDS : 0);
+        return {vis, a.vis_n > w ? a.vis_n : w};
+    }
+}
+constexpr size_t BEAM_LDS_MAX_BYTES = 64 * 1024;  // a workgroup's LDS without an opt-in attribute
+
+// 0, or why no layer-0 launch of the given tier (lds: the LDS list, else the
+// register lists) runs these arguments: -4 past the capacity of the tier's
+// list, -2 when the visited set and the LDS list do not fit a workgroup's LDS
+// (an explicit vis_entries too large for this ef).  Asked by both tiers'
+// launches and, for the tier it precedes, by the pre-pass.
+inline int beam_limits(const SearchArgs& a, bool lds) {
+    if (!lds) return beam_efl(a) > 512 ? -4 : 0;
+    if (beam_efl(a) > LL_MAX_EF) return -4;
+    return (size_t)4 * (size_t)beam_lds<LList>(a).words > BEAM_LDS_MAX_BYTES ? -2 : 0;
+}
 
 // The ordered path splits the descent: the pre-pass walks the layers of the sort
 // key and above, top .. beam_order_lo, and the layer-0 launch walks the rest
@@ -104,34 +135,45 @@ __device__ __forceinline__ void beam_pad_out(const SearchArgs& a, int64_t b, int
     if (lane == 0) a.out_n[b] = nvalid;
 }
 
-template <class C, int R, int G, bool SCREEN, int XW, class BEv>
-__device__ __forceinline__ void beam_query(const SearchArgs& a, int64_t b, const QReg<C>& q, float qn, uint32_t* smem,
+// How the one body reaches the launch's arguments: through a reference in the
+// register kernels and as a copy in the LDS kernel, as each did while it had a
+// body of its own.  The choice only steers the compiler's schedule: with these
+// two the kernels come out as they did before the bodies were shared (the
+// register kernels instruction for instruction, the LDS kernel but for three
+// reordered instructions), and through a reference about a fifth of the LDS
+// kernel's instructions move (profiles/beam_refactor.txt, section 4).
+template <class LT>
+using BeamArgs = std::conditional_t<bl_regs<LT> == 0, const SearchArgs, const SearchArgs&>;
+
+// One query b over list LT: the greedy descent, the layer-0 beam, and its
+// first k live entries into the outputs.  BEv scores each batch of candidates
+// (beam_layer_l).
+template <class C, class LT, int G, bool SCREEN, int XW, class BEv>
+__device__ __forceinline__ void beam_query(BeamArgs<LT> a, int64_t b, const QReg<C>& q, float qn, uint32_t* smem,
                                            WaveStats& st, const BEv& bev) {
     const int lane = lane_id();
     const int vsz = a.vis16 ? -1 : a.vis_n;  // (beam_layer: < 0 selects the compact set)
     const uint32_t ep = beam_descend<C, G, SCREEN>(a, q, qn, smem, vsz, st, bev, beam_entry_of(a, b),
                                                    beam_entry_layer(a), 1, true);
-    BList<R> L;
-    const int efl = a.ef > a.k ? a.ef : a.k;
-    // lists of 256 / 512 entries merge each step's candidates at once, with the
-    // LDS past the visited set as scratch (launch_beam_t sizes the LDS for it;
-    // the default compact set leaves room in the 20 KiB a 2-wave SIMD allows)
-    constexpr bool MRG = R >= 4;
-    float* mrg = MRG ? reinterpret_cast<float*>(smem + beam_vis_words(a)) : nullptr;
-    beam_layer<C, R, G, false, SCREEN, XW, MRG>(a.g, 0, ep, efl, q, qn, L, smem, vsz, st, bev, mrg);
+    LT L;
+    const int efl = beam_efl(a);
+    float* mrg = bl_place(L, smem + beam_lds<LT>(a).list, efl);
+    beam_layer_l<C, LT, G, false, SCREEN, XW, bl_merges<LT>, BEv>(a.g, 0, ep, efl, q, qn, L, smem, vsz, st, bev, mrg);
     // compact the sorted list into the first k live entries (deleted rows
     // route the search but are never returned)
     int nvalid = 0;
     const unsigned long long below = (1ull << lane) - 1ull;
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint32_t id = L.i[r] & ID_MASK;
-        const bool ok = L.i[r] != EMPTY_ID && !is_dead(a.g, id);
+    for (int c = 0; c < bl_span(L); c += 64) {
+        if (bl_regs<LT> == 0 && nvalid >= a.k) break;  // (the LDS list stops early; the registers are all read)
+        const uint32_t w = bl_chunk_id(L, c);
+        const uint32_t id = w & ID_MASK;
+        const bool ok = w != EMPTY_ID && !is_dead(a.g, id);
         const unsigned long long m = __ballot(ok);
         const int pos = nvalid + __popcll(m & below);
         if (ok && pos < a.k) {
             a.out_keys[b * a.k + pos] = a.g.keys[id];
-            a.out_dist[b * a.k + pos] = L.d[r];
+            a.out_dist[b * a.k + pos] = bl_chunk_dist(L, c);
             if (a.out_ids) a.out_ids[b * a.k + pos] = (int32_t)id;
         }
         nvalid += __popcll(m);
@@ -169,6 +211,17 @@ __device__ __forceinline__ void beam_stats(const SearchArgs& a, const WaveStats&
     }
 }
 
+// one wave's whole query: load it, run it (beam_query), add the counters
+template <class C, class LT, int G, bool SCREEN, int XW>
+__device__ __forceinline__ void beam_wave(BeamArgs<LT> a, int64_t b, uint32_t* smem) {
+    QReg<C> q;
+    load_query(q, a.q + (size_t)b * C::PITCH);
+    const float qn = query_norm(q);
+    WaveStats st;
+    beam_query<C, LT, G, SCREEN, XW>(a, b, q, qn, smem, st, WaveBatch());
+    beam_stats(a, st);
+}
+
 // MH_BEAM_WIDE_G / MH_BEAM_WIDE_WAVES (build flags, for tools/ variants): rows
 // in flight per wave step and the waves per SIMD the compiler must fit, for the
 // 512-entry list (R = 8); 0 = the configuration's G and 2 waves
@@ -178,18 +231,15 @@ __device__ __forceinline__ void beam_stats(const SearchArgs& a, const WaveStats&
 #ifndef MH_BEAM_WIDE_WAVES
 #define MH_BEAM_WIDE_WAVES 2
 #endif
+// (the kernels keep their own attributes: the register kernel's waves per SIMD
+// are its register budget, and the recorded profiles go by these names)
 template <class C, int R, int G, bool SCREEN, int XW>
 __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_eu(R >= 8 ? MH_BEAM_WIDE_WAVES : 2)))
 void k_search_beam(SearchArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int64_t b = beam_query_of(a, blockIdx.x);
     if (b < 0) return;
-    QReg<C> q;
-    load_query(q, a.q + (size_t)b * C::PITCH);
-    const float qn = query_norm(q);
-    WaveStats st;
-    beam_query<C, R, G, SCREEN, XW>(a, b, q, qn, smem, st, WaveBatch());
-    beam_stats(a, st);
+    beam_wave<C, BList<R>, G, SCREEN, XW>(a, b, smem);
 }
 
 // ---------------------------------------------------------------------------
@@ -216,7 +266,7 @@ __global__ __launch_bounds__(64 * BMW_WAVES) void k_search_beam_mw(SearchArgs a)
     const float qn = query_norm(q);
     WaveStats st;
     if (wave == 0) {
-        beam_query<C, R, G, SCREEN, 1>(a, b, q, qn, smem, st, MwBatch{&sh});
+        beam_query<C, BList<R>, G, SCREEN, 1>(a, b, q, qn, smem, st, MwBatch{&sh});
         if (lane_id() == 0) sh.cmd = BMW_EXIT;
         bmw_barrier();  // releases the other waves
     } else {
@@ -264,97 +314,52 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_beam_desc
     beam_stats(a, st);
 }
 
-template <class C, int R, int G, int XW>
-static int launch_beam_t(const SearchArgs& a, hipStream_t s) {
-    const size_t lds = (size_t)4 * (size_t)(R >= 4 ? std::max(a.vis_n, beam_vis_words(a) + BL_MERGE_WORDS) : a.vis_n);
-    // small batch: a workgroup per query (the standard search only; a wider
-    // expansion runs the one-wave kernel at every batch size)
-    if constexpr (XW == 1) {
-        if (R <= 2 && beam_small_batch(a) && !a.order) {
-            if (a.g.h16)
-                hipLaunchKernelGGL((k_search_beam_mw<C, R, G, true>), dim3((unsigned)a.B), dim3(64 * BMW_WAVES), lds, s,
-                                   a);
-            else
-                hipLaunchKernelGGL((k_search_beam_mw<C, R, G, false>), dim3((unsigned)a.B), dim3(64 * BMW_WAVES), lds,
-                                   s, a);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        }
-    }
-    const unsigned grid = (unsigned)(a.order ? beam_order_grid(a) : a.B);
-    if (a.g.h16)
-        hipLaunchKernelGGL((k_search_beam<C, R, G, true, XW>), dim3(grid), dim3(64), lds, s, a);
-    else
-        hipLaunchKernelGGL((k_search_beam<C, R, G, false, XW>), dim3(grid), dim3(64), lds, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
 // ---------------------------------------------------------------------------
 // wide lists (beam_lds_min_ef <= max(ef, k) <= LL_MAX_EF): the layer-0 list in
 // LDS (device_search.hpp LList) behind the visited set; one wave per query at
-// every batch size and every XW.  The descent, the step structure, the screen
-// and the visited set are k_search_beam's (beam_layer_l over the other list),
-// so the results are the register lists' at equal ef.
+// every batch size and every XW.  The same body over the other list, so the
+// results are the register lists' at equal ef.
 // ---------------------------------------------------------------------------
 template <class C, int G, bool SCREEN, int XW>
 __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_search_beam_lds(SearchArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int64_t b = beam_query_of(a, blockIdx.x);
     if (b < 0) return;
-    const int lane = lane_id();
-    QReg<C> q;
-    load_query(q, a.q + (size_t)b * C::PITCH);
-    const float qn = query_norm(q);
-    WaveStats st;
-    const WaveBatch bev;
-    const int vsz = a.vis16 ? -1 : a.vis_n;
-    const uint32_t ep = beam_descend<C, G, SCREEN>(a, q, qn, smem, vsz, st, bev, beam_entry_of(a, b),
-                                                   beam_entry_layer(a), 1, true);
-    const int efl = a.ef > a.k ? a.ef : a.k;
-    LList L;
-    ll_place(L, smem + ((beam_vis_words(a) + 3) & ~3), efl);
-    beam_layer_l<C, LList, G, false, SCREEN, XW, true, WaveBatch>(a.g, 0, ep, efl, q, qn, L, smem, vsz, st, bev, nullptr);
-    // the first k live entries (deleted rows route the search but are never returned)
-    int nvalid = 0;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (int c = 0; c < L.n && nvalid < a.k; c += 64) {
-        const int idx = c + lane;
-        const uint32_t w = idx < L.n ? L.i[idx] : EMPTY_ID;
-        const uint32_t id = w & ID_MASK;
-        const bool ok = w != EMPTY_ID && !is_dead(a.g, id);
-        const unsigned long long m = __ballot(ok);
-        const int pos = nvalid + __popcll(m & below);
-        if (ok && pos < a.k) {
-            a.out_keys[b * a.k + pos] = a.g.keys[id];
-            a.out_dist[b * a.k + pos] = L.d[idx];
-            if (a.out_ids) a.out_ids[b * a.k + pos] = (int32_t)id;
-        }
-        nvalid += __popcll(m);
-    }
-    beam_pad_out(a, b, min(nvalid, a.k));
-    beam_stats(a, st);
+    beam_wave<C, LList, G, SCREEN, XW>(a, b, smem);
 }
 
-// the wide tier's dynamic LDS: the visited set, then the list
-inline size_t beam_lds_bytes(const SearchArgs& a) {
-    const int efl = a.ef > a.k ? a.ef : a.k;
-    return (size_t)4 * (size_t)(((beam_vis_words(a) + 3) & ~3) + ll_words(efl));
+// f(std::true_type / std::false_type): the kernels with and without the fp16 screen
+template <class F>
+int beam_with_screen(const SearchArgs& a, F&& f) {
+    return a.g.h16 ? f(std::true_type()) : f(std::false_type());
 }
-constexpr size_t BEAM_LDS_MAX_BYTES = 64 * 1024;  // a workgroup's LDS without an opt-in attribute
-
-// -2: the visited set and the list do not fit a workgroup's LDS (an explicit
-// vis_entries too large for this ef); -4: past the list's capacity
-template <class C, int G, int XW>
-static int launch_beam_lds_t(const SearchArgs& a, hipStream_t s) {
-    const int efl = a.ef > a.k ? a.ef : a.k;
-    if (efl > LL_MAX_EF) return -4;
-    const size_t lds = beam_lds_bytes(a);
-    if (lds > BEAM_LDS_MAX_BYTES) return -2;
-    const unsigned grid = (unsigned)(a.order ? beam_order_grid(a) : a.B);
-    if (a.g.h16)
-        hipLaunchKernelGGL((k_search_beam_lds<C, G, true, XW>), dim3(grid), dim3(64), lds, s, a);
-    else
-        hipLaunchKernelGGL((k_search_beam_lds<C, G, false, XW>), dim3(grid), dim3(64), lds, s, a);
+template <class K>
+int beam_launch(K kernel, int64_t grid, int block, int lds_words, const SearchArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), (size_t)4 * (size_t)lds_words, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// the layer-0 launch over list LT
+template <class C, class LT, int G, int XW>
+static int launch_beam_t(const SearchArgs& a, hipStream_t s) {
+    static_assert(bl_regs<LT> >= 0, "BList<R> or LList");
+    const int lds = beam_lds<LT>(a).words;
+    return beam_with_screen(a, [&](auto screen) {
+        constexpr bool SC = decltype(screen)::value;
+        constexpr int R = bl_regs<LT>;
+        // small batch: a workgroup per query (the standard search on the narrow
+        // register lists only; a wider expansion and the LDS list run the one-wave
+        // kernel at every batch size)
+        if constexpr (XW == 1 && R >= 1) {
+            if (R <= 2 && beam_small_batch(a) && !a.order)
+                return beam_launch(k_search_beam_mw<C, R, G, SC>, a.B, 64 * BMW_WAVES, lds, a, s);
+        }
+        const int64_t grid = a.order ? beam_order_grid(a) : a.B;
+        if constexpr (R == 0)
+            return beam_launch(k_search_beam_lds<C, G, SC, XW>, grid, 64, lds, a, s);
+        else
+            return beam_launch(k_search_beam<C, R, G, SC, XW>, grid, 64, lds, a, s);
+    });
 }
 
 // group width G of configuration (L, V), from MH_FOR_EACH_CFG
@@ -369,42 +374,32 @@ constexpr int beam_group() {
 
 template <int L, int V, int XW>
 int launch_beam_cfg(const SearchArgs& a, hipStream_t s) {
-    constexpr int G = beam_group<L, V>();
-    const int efl = a.ef > a.k ? a.ef : a.k;
-    if (efl <= 64) return launch_beam_t<Cfg<L, V>, 1, G, XW>(a, s);
-    if (efl <= 128) return launch_beam_t<Cfg<L, V>, 2, G, XW>(a, s);
-    if (efl <= 256) return launch_beam_t<Cfg<L, V>, 4, G, XW>(a, s);
-    constexpr int GW = MH_BEAM_WIDE_G > 0 && MH_BEAM_WIDE_G < G ? MH_BEAM_WIDE_G : G;
-    if (efl <= 512) return launch_beam_t<Cfg<L, V>, 8, GW, XW>(a, s);
-    return -4;
-}
-
-// instantiated per XW in beam_wa-wc.hip
-template <int L, int V, int XW>
-int launch_beam_lds_cfg(const SearchArgs& a, hipStream_t s) {
-    return launch_beam_lds_t<Cfg<L, V>, beam_group<L, V>(), XW>(a, s);
-}
-
-// the ordered path's pre-pass (k_beam_descend), instantiated in beam_desc.hip.
-// The same failures as the layer-0 launch it precedes: -4 past the LDS list's
-// capacity, -2 when the visited set and the list do not fit a workgroup's LDS.
-template <int L, int V>
-int launch_beam_descend_cfg(const SearchArgs& a, hipStream_t s) {
     using C = Cfg<L, V>;
     constexpr int G = beam_group<L, V>();
-    const int efl = a.ef > a.k ? a.ef : a.k;
-    if (efl >= a.lds_min_ef) {
-        if (efl > LL_MAX_EF) return -4;
-        if (beam_lds_bytes(a) > BEAM_LDS_MAX_BYTES) return -2;
-    } else if (efl > 512) {
-        return -4;
-    }
-    const size_t lds = (size_t)4 * (size_t)std::max(a.vis_n, beam_vis_words(a));
-    if (a.g.h16)
-        hipLaunchKernelGGL((k_beam_descend<C, G, true>), dim3((unsigned)a.B), dim3(64), lds, s, a);
-    else
-        hipLaunchKernelGGL((k_beam_descend<C, G, false>), dim3((unsigned)a.B), dim3(64), lds, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    if (const int rc = beam_limits(a, false)) return rc;
+    const int efl = beam_efl(a);
+    if (efl <= 64) return launch_beam_t<C, BList<1>, G, XW>(a, s);
+    if (efl <= 128) return launch_beam_t<C, BList<2>, G, XW>(a, s);
+    if (efl <= 256) return launch_beam_t<C, BList<4>, G, XW>(a, s);
+    constexpr int GW = MH_BEAM_WIDE_G > 0 && MH_BEAM_WIDE_G < G ? MH_BEAM_WIDE_G : G;
+    return launch_beam_t<C, BList<8>, GW, XW>(a, s);  // (beam_limits: efl <= 512)
+}
+
+template <int L, int V, int XW>
+int launch_beam_lds_cfg(const SearchArgs& a, hipStream_t s) {
+    if (const int rc = beam_limits(a, true)) return rc;
+    return launch_beam_t<Cfg<L, V>, LList, beam_group<L, V>(), XW>(a, s);
+}
+
+// the ordered path's pre-pass (k_beam_descend); it fails as the layer-0 launch
+// it precedes would (beam_limits)
+template <int L, int V>
+int launch_beam_descend_cfg(const SearchArgs& a, hipStream_t s) {
+    if (const int rc = beam_limits(a, beam_in_lds(a))) return rc;
+    const int lds = beam_lds<BList<1>>(a).words;  // (the visited set alone)
+    return beam_with_screen(a, [&](auto screen) {
+        return beam_launch(k_beam_descend<Cfg<L, V>, beam_group<L, V>(), decltype(screen)::value>, a.B, 64, lds, a, s);
+    });
 }
 
 }  // namespace mh

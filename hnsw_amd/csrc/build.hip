@@ -1728,6 +1728,7 @@ static int launch_batch_search_t(const BatchBuildArgs& a, hipStream_t s) {
 #ifndef MH_PART
 #define MH_PART 0
 #endif
+#undef MH_FOR_EACH_CFG  // (engine.hpp: the whole table)
 #if MH_PART == 0
 #define MH_FOR_EACH_CFG(X) X(16, 1, 2) X(32, 1, 4) X(64, 1, 8)
 #elif MH_PART == 1

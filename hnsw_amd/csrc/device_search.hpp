@@ -622,6 +622,58 @@ __device__ __forceinline__ int bl_seed(const LList& L, uint32_t* vis, int vsize)
     return seeded;
 }
 
+// What the query kernels' one body (beam.hpp beam_query) asks of its list
+// besides beam_layer_l's operations:
+//   bl_regs<LT>            its registers per lane, R of BList<R>; 0: the list
+//                          lives in LDS (LList)
+//   bl_merges<LT>          its layer-0 steps go through bl_merge: lists of 256 /
+//                          512 entries in registers, and every LDS list
+//   bl_place(L, mem, efl)  the list's LDS part goes to mem (beam.hpp beam_lds
+//                          says where that is and how long); returns beam_layer_l's mrg
+//   bl_span(L)             the entries to scan for the outputs, in chunks of 64 from
+//                          entry 0: 64 R, or the filled part of the LDS list
+//   bl_chunk_id(L, e)      the chunk at entry e (a multiple of 64): entry e + lane's
+//                          id word in each lane (EMPTY_ID past the filled entries),
+//                          and bl_chunk_dist(L, e) its distance (read only for an
+//                          entry that is there)
+template <class LT>
+constexpr int bl_regs = -1;  // (only these two lists: another type finds none of the bl_* overloads)
+template <>
+inline constexpr int bl_regs<LList> = 0;
+template <int R>
+constexpr int bl_regs<BList<R>> = R;
+template <class LT>
+constexpr bool bl_merges = bl_regs<LT> == 0 || bl_regs<LT> >= 4;
+
+template <int R>
+__device__ __forceinline__ float* bl_place(BList<R>&, uint32_t* mem, int) {
+    return bl_merges<BList<R>> ? reinterpret_cast<float*>(mem) : nullptr;  // (bl_merge's scratch, BL_MERGE_WORDS)
+}
+__device__ __forceinline__ float* bl_place(LList& L, uint32_t* mem, int efl) {
+    ll_place(L, mem, efl);
+    return nullptr;  // (the candidate buffer is part of the list: bl_cbuf)
+}
+
+// (BList: e is the index of an unrolled loop, so the registers are indexed at compile time)
+template <int R>
+__device__ __forceinline__ constexpr int bl_span(const BList<R>&) {
+    return R * 64;
+}
+template <int R>
+__device__ __forceinline__ uint32_t bl_chunk_id(const BList<R>& L, int e) {
+    return L.i[e >> 6];
+}
+template <int R>
+__device__ __forceinline__ float bl_chunk_dist(const BList<R>& L, int e) {
+    return L.d[e >> 6];
+}
+__device__ __forceinline__ int bl_span(const LList& L) { return L.n; }
+__device__ __forceinline__ uint32_t bl_chunk_id(const LList& L, int e) {
+    const int idx = e + lane_id();
+    return idx < L.n ? L.i[idx] : EMPTY_ID;
+}
+__device__ __forceinline__ float bl_chunk_dist(const LList& L, int e) { return L.d[e + lane_id()]; }
+
 // How beam_layer scores one batch of new candidates (ids in lanes 0..cnt-1 of
 // cid) and hands the survivors to its sink: WaveBatch does it on the calling
 // wave; the multi-wave single-query kernel (beam.hpp MwBatch) spreads the rows

@@ -28,6 +28,31 @@ inline bool pick_cfg(int dim, int& lpr, int& vpl) {
 }
 inline int pitch_of(int lpr, int vpl) { return lpr * 4 * vpl; }
 
+// The same configurations as X(lpr, vpl, G), for the code that instantiates or
+// selects a kernel per configuration.  G: the group width, rows in flight per
+// wave step.  In four groups: the units of beam_units.hip and walks_units.hip
+// each instantiate one or two of them, so that they compile in parallel.
+// (build.hip compiles in parts, each with its own statement of its group.)
+#define MH_CFGS_A(X) X(16, 1, 2) X(32, 1, 4) X(64, 1, 8)
+#define MH_CFGS_B(X) X(64, 2, 8) X(64, 3, 8)
+#define MH_CFGS_C(X) X(64, 4, 4) X(64, 6, 4)
+#define MH_CFGS_D(X) X(64, 8, 2) X(64, 12, 1) X(64, 16, 1)
+#define MH_FOR_EACH_CFG(X) MH_CFGS_A(X) MH_CFGS_B(X) MH_CFGS_C(X) MH_CFGS_D(X)
+
+// f(DimCfg<L, V, G>()) for the configuration (lpr, vpl) of the table; -3: not in it
+template <int L_, int V_, int G_>
+struct DimCfg {
+    static constexpr int L = L_, V = V_, G = G_;
+};
+template <class F>
+int with_cfg(int lpr, int vpl, F&& f) {
+#define X_(L, V, G) \
+    if (lpr == L && vpl == V) return f(DimCfg<L, V, G>());
+    MH_FOR_EACH_CFG(X_)
+#undef X_
+    return -3;
+}
+
 struct SearchArgs {
     GraphDev g;
     const float* q;  // padded queries [B * pitch]

@@ -1906,74 +1906,52 @@ int launch_exact_select(const ExactArgs& a, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-#define MH_FOR_EACH_CFG(X) \
-    X(16, 1, 2)            \
-    X(32, 1, 4)            \
-    X(64, 1, 8)            \
-    X(64, 2, 8)            \
-    X(64, 3, 8)            \
-    X(64, 4, 4)            \
-    X(64, 6, 4)            \
-    X(64, 8, 2)            \
-    X(64, 12, 1)           \
-    X(64, 16, 1)
-
 int launch_rerank(const float* Q, const GraphDev& g, const uint32_t* cand, int kk, int64_t B, int lpr, int vpl, int k,
                   int64_t* out_keys, float* out_dist, int32_t* out_n, int32_t* out_ids, const CertArgs& c,
                   hipStream_t s) {
     if (B <= 0) return 0;
     if (k > 256 || kk > 256 || k > kk) return -4;
-#define X_(L, V, G)                                                                                              \
-    if (lpr == L && vpl == V) {                                                                                  \
-        if (k <= 64)                                                                                             \
-            hipLaunchKernelGGL((k_rerank<Cfg<L, V>, G, 1>), dim3((unsigned)B), dim3(64), 0, s, Q, g, cand, kk, B, k, \
-                               out_keys, out_dist, out_n, out_ids, c);                                           \
-        else                                                                                                     \
-            hipLaunchKernelGGL((k_rerank<Cfg<L, V>, G, 4>), dim3((unsigned)B), dim3(64), 0, s, Q, g, cand, kk, B, k, \
-                               out_keys, out_dist, out_n, out_ids, c);                                           \
-        return hipGetLastError() == hipSuccess ? 0 : -1;                                                         \
-    }
-    MH_FOR_EACH_CFG(X_)
-#undef X_
-    return -3;
+    return with_cfg(lpr, vpl, [&](auto cfg) {
+        using C = Cfg<cfg.L, cfg.V>;
+        if (k <= 64)
+            hipLaunchKernelGGL((k_rerank<C, cfg.G, 1>), dim3((unsigned)B), dim3(64), 0, s, Q, g, cand, kk, B, k, out_keys,
+                               out_dist, out_n, out_ids, c);
+        else
+            hipLaunchKernelGGL((k_rerank<C, cfg.G, 4>), dim3((unsigned)B), dim3(64), 0, s, Q, g, cand, kk, B, k, out_keys,
+                               out_dist, out_n, out_ids, c);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    });
 }
 
 int launch_exact_fallback(const float* Q, const GraphDev& g, int64_t N, const int32_t* flagged, const int32_t* nflag,
                           float* scores, int64_t ldS, int lpr, int vpl, hipStream_t s) {
     if (N <= 0) return 0;
-#define X_(L, V, G)                                                                                          \
-    if (lpr == L && vpl == V) {                                                                              \
-        hipLaunchKernelGGL((k_exact_fallback<Cfg<L, V>, (G < 4 ? G : 4)>), dim3(1024), dim3(256), 0, s, Q, g, N, \
-                           flagged, nflag, scores, ldS);                                                     \
-        return hipGetLastError() == hipSuccess ? 0 : -1;                                                     \
-    }
-    MH_FOR_EACH_CFG(X_)
-#undef X_
-    return -3;
+    return with_cfg(lpr, vpl, [&](auto c) {
+        hipLaunchKernelGGL((k_exact_fallback<Cfg<c.L, c.V>, (c.G < 4 ? c.G : 4)>), dim3(1024), dim3(256), 0, s, Q, g, N,
+                           flagged, nflag, scores, ldS);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    });
 }
 
 int launch_fallback_select(const float* Q, const GraphDev& g, const ExactArgs& a, int lpr, int vpl, hipStream_t s) {
     if (a.B <= 0 || a.N <= 0) return 0;
     if (a.kk < 1 || a.kk > 256 || a.nseg < 1 || a.nseg * a.kk > SEL_MERGE_MAX || !a.only) return -4;
     const dim3 grid((unsigned)(a.B * a.nseg));
-#define X_(L, V, G)                                                                                            \
-    if (lpr == L && vpl == V) {                                                                                \
-        constexpr int GF = G < 4 ? G : 4;                                                                      \
-        if (a.kk <= 64)                                                                                        \
-            hipLaunchKernelGGL((k_fallback_select<Cfg<L, V>, GF, 1>), grid, dim3(256), 0, s, Q, g, a.N, a.only, \
-                               a.kk, a.nseg, a.seglen, a.seg_d, a.seg_i);                                       \
-        else if (a.kk <= 128)                                                                                  \
-            hipLaunchKernelGGL((k_fallback_select<Cfg<L, V>, GF, 2>), grid, dim3(256), 0, s, Q, g, a.N, a.only, \
-                               a.kk, a.nseg, a.seglen, a.seg_d, a.seg_i);                                       \
-        else                                                                                                   \
-            hipLaunchKernelGGL((k_fallback_select<Cfg<L, V>, GF, 4>), grid, dim3(256), 0, s, Q, g, a.N, a.only, \
-                               a.kk, a.nseg, a.seglen, a.seg_d, a.seg_i);                                       \
-        hipLaunchKernelGGL(k_select_merge, dim3((unsigned)a.B), dim3(64), 0, s, a);                            \
-        return hipGetLastError() == hipSuccess ? 0 : -1;                                                       \
-    }
-    MH_FOR_EACH_CFG(X_)
-#undef X_
-    return -3;
+    return with_cfg(lpr, vpl, [&](auto c) {
+        using C = Cfg<c.L, c.V>;
+        constexpr int GF = c.G < 4 ? c.G : 4;
+        if (a.kk <= 64)
+            hipLaunchKernelGGL((k_fallback_select<C, GF, 1>), grid, dim3(256), 0, s, Q, g, a.N, a.only, a.kk, a.nseg,
+                               a.seglen, a.seg_d, a.seg_i);
+        else if (a.kk <= 128)
+            hipLaunchKernelGGL((k_fallback_select<C, GF, 2>), grid, dim3(256), 0, s, Q, g, a.N, a.only, a.kk, a.nseg,
+                               a.seglen, a.seg_d, a.seg_i);
+        else
+            hipLaunchKernelGGL((k_fallback_select<C, GF, 4>), grid, dim3(256), 0, s, Q, g, a.N, a.only, a.kk, a.nseg,
+                               a.seglen, a.seg_d, a.seg_i);
+        hipLaunchKernelGGL(k_select_merge, dim3((unsigned)a.B), dim3(64), 0, s, a);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    });
 }
 
 int launch_merge_topk(const int64_t* keys_in, const float* dist_in, const int32_t* n_in, int shards, int64_t B, int k,

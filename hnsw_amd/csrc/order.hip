@@ -1,7 +1,7 @@
 // order.hip -- the ordered beam search's sort (search_host.cpp, option
 // "search_order"): the descent pre-pass's 64-bit path keys into the permutation
 // order[B], with rocPRIM's device radix sort.  A unit of its own: the sort's
-// templates take as long to compile as a beam_*.hip unit.
+// templates take as long to compile as a unit of beam_units.hip.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "engine.hpp"

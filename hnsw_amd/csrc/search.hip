@@ -9,7 +9,7 @@
 #include "walks.hpp"
 
 namespace mh {
-// instantiated in beam_*.hip / walks_*.hip
+// instantiated in the units of beam_units.hip / walks_units.hip
 #define X_(L, V, G)                                                                    \
     extern template int launch_beam_cfg<L, V, 1>(const SearchArgs&, hipStream_t);    \
     extern template int launch_beam_cfg<L, V, 2>(const SearchArgs&, hipStream_t);    \
@@ -396,72 +396,47 @@ int launch_h16_rows(const float* X, const float* norms, int64_t n0, int64_t n1, 
 }
 
 int launch_norms(const float* X, int64_t n0, int64_t n1, int pitch, int lpr, int vpl, float* out, hipStream_t s) {
-#define X_(L, V, G) \
-    if (lpr == L && vpl == V) return launch_norms_t<Cfg<L, V>>(X, n0, n1, pitch, out, s);
-    MH_FOR_EACH_CFG(X_)
-#undef X_
-    return -3;
+    return with_cfg(lpr, vpl, [&](auto c) { return launch_norms_t<Cfg<c.L, c.V>>(X, n0, n1, pitch, out, s); });
 }
 
 int launch_sweep(const float* q, const float* X, int64_t n, int pitch, int lpr, int vpl, int metric, float* out,
                  hipStream_t s) {
-#define X_(L, V, G) \
-    if (lpr == L && vpl == V) return launch_sweep_t<Cfg<L, V>, G>(q, X, n, pitch, metric, out, s);
-    MH_FOR_EACH_CFG(X_)
-#undef X_
-    return -3;
+    return with_cfg(lpr, vpl,
+                    [&](auto c) { return launch_sweep_t<Cfg<c.L, c.V>, c.G>(q, X, n, pitch, metric, out, s); });
+}
+
+// f(std::integral_constant<int, XW>()) for the option search_expand (2, 4, else the standard 1)
+template <class F>
+static int with_expand(int expand, F&& f) {
+    return expand == 4   ? f(std::integral_constant<int, 4>())
+           : expand == 2 ? f(std::integral_constant<int, 2>())
+                         : f(std::integral_constant<int, 1>());
 }
 
 int launch_search_beam(const SearchArgs& a, int lpr, int vpl, hipStream_t s) {
     if (a.B <= 0) return 0;
-    // the LDS-resident list from max(ef, k) = lds_min_ef (513 unless the option
-    // beam_lds_min_ef lowers it: past the widest register list)
-    if (std::max(a.ef, a.k) >= a.lds_min_ef) {
-#define X_(L, V, G)                                                   \
-    if (lpr == L && vpl == V)                                         \
-        return a.expand == 4 ? launch_beam_lds_cfg<L, V, 4>(a, s)     \
-               : a.expand == 2 ? launch_beam_lds_cfg<L, V, 2>(a, s)   \
-                               : launch_beam_lds_cfg<L, V, 1>(a, s);
-        MH_FOR_EACH_CFG(X_)
-#undef X_
-        return -3;
-    }
-#define X_(L, V, G)                                                   \
-    if (lpr == L && vpl == V)                                         \
-        return a.expand == 4 ? launch_beam_cfg<L, V, 4>(a, s)         \
-               : a.expand == 2 ? launch_beam_cfg<L, V, 2>(a, s)       \
-                               : launch_beam_cfg<L, V, 1>(a, s);
-    MH_FOR_EACH_CFG(X_)
-#undef X_
-    return -3;
+    const bool lds = beam_in_lds(a);  // the tier
+    return with_expand(a.expand, [&](auto xw) {
+        return with_cfg(lpr, vpl, [&](auto c) {
+            return lds ? launch_beam_lds_cfg<c.L, c.V, xw.value>(a, s) : launch_beam_cfg<c.L, c.V, xw.value>(a, s);
+        });
+    });
 }
 
 int launch_beam_descend(const SearchArgs& a, int lpr, int vpl, hipStream_t s) {
     if (a.B <= 0) return 0;
-#define X_(L, V, G) \
-    if (lpr == L && vpl == V) return launch_beam_descend_cfg<L, V>(a, s);
-    MH_FOR_EACH_CFG(X_)
-#undef X_
-    return -3;
+    return with_cfg(lpr, vpl, [&](auto c) { return launch_beam_descend_cfg<c.L, c.V>(a, s); });
 }
 
 int launch_negatives(const NegArgs& a, int lpr, int vpl, hipStream_t s) {
     if (a.B <= 0) return 0;
     if (a.kx > NEG_MAX_CAND) return -4;
-#define X_(L, V, G) \
-    if (lpr == L && vpl == V) return launch_negatives_cfg<L, V>(a, s);
-    MH_FOR_EACH_CFG(X_)
-#undef X_
-    return -3;
+    return with_cfg(lpr, vpl, [&](auto c) { return launch_negatives_cfg<c.L, c.V>(a, s); });
 }
 
 int launch_search_compat(const SearchArgs& a, int lpr, int vpl, hipStream_t s) {
     if (a.B <= 0) return 0;
-#define X_(L, V, G) \
-    if (lpr == L && vpl == V) return launch_compat_cfg<L, V>(a, s);
-    MH_FOR_EACH_CFG(X_)
-#undef X_
-    return -3;
+    return with_cfg(lpr, vpl, [&](auto c) { return launch_compat_cfg<c.L, c.V>(a, s); });
 }
 
 }  // namespace mh

@@ -1,7 +1,7 @@
 // walks.hpp -- the reference-semantics search kernel (k_search_compat,
 // graph.go:571-622) and the negatives epilogue (k_negatives,
-// graph.go:1116-1537), instantiated per dimension configuration in
-// walks_*.hip (split from search.hip so the configurations compile in
+// graph.go:1116-1537), instantiated per dimension configuration in the units
+// of walks_units.hip (split from search.hip so the configurations compile in
 // parallel).
 #pragma once
 #include "beam.hpp"

@@ -6,9 +6,11 @@ compared bit for bit with the oracle's restatement of the search
 (oracle.c beam_layer_search, any ef): both metrics, search_expand 1 / 2 / 4, the
 fp16 screen on and off, the compact and the 32-bit visited set, sets small
 enough to forget on every query, lists that never fill, tied distances (the
-sequential fallback of the merge), deleted rows, small batches and the
-negatives path.  Option beam_lds_min_ef lowers the tier's threshold so that the
-LDS list also runs against the register lists at equal ef.
+sequential fallback of the merge), deleted rows (unlinked by the batched
+repair, and left inside the lists by reference-semantics deletes), small
+batches and the negatives path.  Option beam_lds_min_ef lowers the tier's
+threshold so that the LDS list also runs against the register lists at equal
+ef.
 """
 import numpy as np
 import pytest
@@ -200,6 +202,84 @@ def test_wide_ef_after_deletes(H, O):
         g.close()
 
 
+@pytest.fixture(scope="module")
+def dangling(H, O):
+    """per metric: a reference-semantics graph whose deletes leave dangling
+    edges (BatchDelete on a compat build isolates the rows but live rows keep
+    their edges to them, so deleted rows enter the layer-0 lists), mirrored
+    into the oracle, and a second oracle copy with the dead flags cleared,
+    which returns the lists as they stand before the dead rows are dropped"""
+    out = {}
+    for metric in (0, 1):
+        rng = np.random.default_rng(17)
+        n, d = 1500, 24
+        X = rng.uniform(-1, 1, (n, d)).astype(np.float32)
+        Q = rng.uniform(-1, 1, (32, d)).astype(np.float32)
+        keys = np.arange(n, dtype=np.int64) * 3 + 1
+        g = H.Graph(M=8, Ml=0.25, EfSearch=20, Distance=_metric_fn(H, metric), Rng=11)
+        g.add_arrays(keys, X)
+        gone = [int(x) for x in keys[::4]]
+        assert all(g.BatchDelete(gone))
+        ex = g.export()
+        o = O.Graph(metric=metric, order=O.ORDER_DEV, M=8, Ml=0.25, EfSearch=20)
+        o.import_graph(**ex)
+        raw = O.Graph(metric=metric, order=O.ORDER_DEV, M=8, Ml=0.25, EfSearch=20)
+        raw.import_graph(**dict(ex, dead=np.zeros_like(ex["dead"])))
+        out[metric] = (g, o, raw, Q, set(gone))
+    yield out
+    for g, *_ in out.values():
+        g.close()
+
+
+@pytest.mark.parametrize("metric", [0, 1])
+def test_dead_rows_sit_in_the_lists(O, dangling, metric):
+    """the fixture is worth something: with the dead flags cleared, at least
+    half of the queries hold a deleted key among the first 64 entries of their
+    ef = 200 list and another past entry 64 (both chunks of the register list,
+    the first and a later chunk of the LDS list)"""
+    _, _, raw, Q, gone = dangling[metric]
+    rk, _, rn = raw.search(Q, 200, mode=O.MODE_BEAM, ef=200)
+    both = 0
+    for b in range(len(Q)):
+        head = any(int(x) in gone for x in rk[b, :min(rn[b], 64)])
+        tail = any(int(x) in gone for x in rk[b, 64:rn[b]])
+        both += head and tail
+    assert both >= len(Q) // 2, both
+
+
+@pytest.mark.parametrize("metric", [0, 1])
+@pytest.mark.parametrize("xw", [1, 4])
+def test_wide_ef_dead_rows_in_list(H, O, dangling, metric, xw):
+    """deleted rows inside the list, ef = 200 on both tiers, fused and ordered
+    launch: the first k live entries are the oracle's for k inside the first
+    chunk, on a chunk edge, past it and at k = ef, where the list runs out of
+    live rows and the tail is padded"""
+    g, o, _, Q, gone = dangling[metric]
+    ef = 200
+    ks = (10, 64, 65, 130, 200)
+    ref = {k: _oracle(O, o, Q, k, ef, xw) for k in ks}
+    old = _with(g, search_expand=xw, search_order=0, search_order_min_b=1, beam_lds_min_ef=513)
+    try:
+        for order in (0, 1):
+            g.set_option("search_order", order)
+            for k in ks:
+                g.set_option("beam_lds_min_ef", 513)
+                reg = g.search_arrays(Q, k, mode=H.MODE_BEAM, ef=ef)
+                g.set_option("beam_lds_min_ef", 65)
+                lds = g.search_arrays(Q, k, mode=H.MODE_BEAM, ef=ef)
+                _same_results(*lds, *reg)
+                _same_results(*lds, *ref[k])
+                for gk, gd, gn in (reg, lds):
+                    assert not (set(gk[gk >= 0].tolist()) & gone), (order, k)
+                    if k == ef:
+                        assert (gn < ef).all() and (gn > 0).all()
+                        for b in range(len(Q)):
+                            assert (gk[b, gn[b]:] == -1).all(), b
+                            assert np.isposinf(gd[b, gn[b]:]).all(), b
+    finally:
+        _with(g, **old)
+
+
 def test_wide_ef_small_batches(H, O, built):
     """B = 1 and B = 7 equal the same queries inside the 32-query batch"""
     g, o, Q = built[1]
@@ -244,15 +324,21 @@ def test_wide_ef_limits(H, built):
         g.search_arrays(Q, 10, mode=H.MODE_BEAM, ef=2049)
     with pytest.raises(H.HnswError, match=r"max\(ef,k\) <= 2048"):
         g.search_arrays(Q, 2049, mode=H.MODE_BEAM, ef=64)
-    # an explicit visited set that does not fit a workgroup's LDS next to the
-    # list is refused on the host, not launched
-    old = _with(g, vis_compact=0, vis_entries=32768)
+    # an explicit visited set that does not fit a workgroup's LDS, next to the
+    # list, is refused on the host, not launched: by the fused launch and, on the
+    # ordered path, by the pre-pass in front of it (the same check)
+    old = _with(g, vis_compact=0, vis_entries=32768, search_order=0, search_order_min_b=1)
     try:
-        with pytest.raises(H.HnswError, match="LDS budget exceeded"):
-            g.search_arrays(Q, 10, mode=H.MODE_BEAM, ef=600)
+        for order in (0, 1):
+            g.set_option("search_order", order)
+            with pytest.raises(H.HnswError, match="LDS budget exceeded"):
+                g.search_arrays(Q, 10, mode=H.MODE_BEAM, ef=600)
     finally:
         g.set_option("vis_entries", 0)
-        g.set_option("vis_compact", old["vis_compact"])
+        _with(g, **{k: v for k, v in old.items() if k != "vis_entries"})
+    for k, v in old.items():
+        if k != "vis_entries":
+            assert g.get_option(k) == v
     assert g.get_option("beam_lds_min_ef") == 513
     for bad in (64, 514):
         with pytest.raises(H.HnswError, match=r"beam_lds_min_ef must be in \[65, 513\]"):
