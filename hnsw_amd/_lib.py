@@ -42,6 +42,14 @@ SIGNATURES = {
     "mhnsw_search_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp,
                                       _vp]),
     "mhnsw_device_status": (C.c_int, [_vp]),
+    "mhnsw_filter_create": (C.c_int, [_vp, _i64p, C.c_int64, _P(C.c_int)]),
+    "mhnsw_filter_update": (C.c_int, [_vp, C.c_int, _i64p, C.c_int64, C.c_int]),
+    "mhnsw_filter_count": (C.c_int, [_vp, C.c_int, _i64p]),
+    "mhnsw_filter_destroy": (C.c_int, [_vp, C.c_int]),
+    "mhnsw_search_filtered": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i64p,
+                                        _f32p, _i32p]),
+    "mhnsw_search_filtered_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp,
+                                               _vp, _vp, _vp]),
     "mhnsw_search_negatives": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, _f32p, _i32p, C.c_int, C.c_float, C.c_int,
                                          C.c_int, C.c_int, _i64p, _f32p, _i32p]),
     "mhnsw_len": (C.c_int64, [_vp]),

@@ -152,6 +152,41 @@ int ensure_capacity(mhnsw_index* h, int64_t need) {
     return 0;
 }
 
+// every filter gone (Import / Load / destroy); enqueued searches have finished
+void drop_filters(mhnsw_index* h) {
+    for (auto& F : h->filters)
+        if (F.d) (void)hipFree(F.d);
+    h->filters.clear();
+    h->filters_dirty = true;
+}
+
+// Every filter's bitmap covers the row capacity (it grows zero-filled: rows
+// added since are not allowed), and the device table of the bitmaps is current.
+// The caller has let the enqueued searches finish when a bitmap may move.
+int filters_fit(mhnsw_index* h) {
+    const size_t words = (size_t)((std::max<int64_t>(h->capn, 1) + 31) / 32);
+    for (auto& F : h->filters) {
+        if (!F.used || (F.d && F.bits.size() >= words)) continue;
+        uint32_t* nd = nullptr;
+        if (hipMalloc(&nd, words * 4) != hipSuccess)
+            return fail(h, MHNSW_ENOMEM, "device allocation of %zu bytes failed", words * 4);
+        F.bits.resize(words, 0u);
+        if (F.d) (void)hipFree(F.d);
+        F.d = nd;
+        HIPCHK(h, hipMemcpyAsync(F.d, F.bits.data(), words * 4, hipMemcpyHostToDevice, h->stream));
+        h->filters_dirty = true;
+    }
+    if (!h->filters_dirty) return 0;
+    if (!h->d_filters && hipMalloc(&h->d_filters, MHNSW_MAX_FILTERS * sizeof(uint32_t*)) != hipSuccess)
+        return fail(h, MHNSW_ENOMEM, "device allocation of the filter table failed");
+    std::vector<const uint32_t*> tab(MHNSW_MAX_FILTERS, nullptr);
+    for (size_t f = 0; f < h->filters.size(); ++f) tab[f] = h->filters[f].used ? h->filters[f].d : nullptr;
+    HIPCHK(h, hipMemcpyAsync(h->d_filters, tab.data(), tab.size() * sizeof(uint32_t*), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->filters_dirty = false;
+    return 0;
+}
+
 // mirror the per-layer pointers into the device table read by the kernels
 int sync_layer_table(mhnsw_index* h) {
     LayerDev t[MH_MAXL];
@@ -1120,6 +1155,9 @@ void mhnsw_destroy(mhnsw_index* h) {
     F(h->xgone.p);
     F(h->xflagged.p);
     F(h->xnflag.p);
+    drop_filters(h);
+    F(h->d_filters);
+    F(h->fof.p);
     if (h->scr_ev) (void)hipEventDestroy(h->scr_ev);
     if (h->meta_ev) (void)hipEventDestroy(h->meta_ev);
     if (h->ord_ev) (void)hipEventDestroy(h->ord_ev);
@@ -1259,6 +1297,9 @@ int mhnsw_set_option(mhnsw_index* h, const char* name, int64_t v) {
     } else if (n == "vis_compact") {
         if (v != 0 && v != 1) return fail(h, MHNSW_EINVAL, "vis_compact must be 0 or 1");
         h->vis_compact = (int)v;
+    } else if (n == "filter_route") {
+        if (v < 1 || v > 2048) return fail(h, MHNSW_EINVAL, "filter_route must be in [1, 2048]");
+        h->filter_route = (int)v;
     } else if (n == "time_build") {
         h->time_build = (int)(v != 0);
     } else if (n == "max_rows") {
@@ -1333,6 +1374,7 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
     else if (n == "screen") *v = h->screen;
     else if (n == "fuse_descent") *v = h->fuse_descent;
     else if (n == "vis_compact") *v = h->vis_compact;
+    else if (n == "filter_route") *v = h->filter_route;
     else if (n == "time_build") *v = h->time_build;
     else if (n == "max_rows") *v = h->max_rows;
     else if (n == "strkey_relabels") *v = h->relabels;
@@ -1416,7 +1458,99 @@ int mhnsw_device_status(mhnsw_index* h) {
     if (!err) return MHNSW_OK;
     HIPCHK(h, hipMemset(h->d_err + 1, 0, sizeof(int)));
     if (err & 4) return fail(h, MHNSW_EINTERNAL, "out-of-range node id in adjacency (graph corrupt)");
+    if (err & 8) return fail(h, MHNSW_EINVAL, "unknown filter in filter_of");
     return fail(h, MHNSW_EINTERNAL, "visited set overflow (raise vis_log2)");
+}
+
+// ---- filters (filtered search) ----
+static int filter_slot(mhnsw_index* h, int f) {
+    if (f < 0 || f >= (int)h->filters.size() || !h->filters[f].used) return fail(h, MHNSW_EINVAL, "unknown filter %d", f);
+    return 0;
+}
+
+// set or clear the bits of the keys' live layer-0 rows and upload the bitmap
+static int filter_apply(mhnsw_index* h, int f, const int64_t* keys, int64_t n, int allow) {
+    mhnsw_index::Filter& F = h->filters[f];
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t r = key_row_in(h, keys[i], 0);
+        if (r < 0) continue;
+        if (allow)
+            F.bits[(size_t)r >> 5] |= 1u << (r & 31);
+        else
+            F.bits[(size_t)r >> 5] &= ~(1u << (r & 31));
+    }
+    if (!F.bits.empty()) {
+        HIPCHK(h, hipMemcpyAsync(F.d, F.bits.data(), F.bits.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return 0;
+}
+
+int mhnsw_filter_create(mhnsw_index* h, const int64_t* keys, int64_t n, int* out_filter) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    if (!out_filter || (n > 0 && !keys)) return fail(h, MHNSW_EINVAL, "keys and out_filter must be non-NULL");
+    int r = drain(h);
+    if (r) return r;
+    int f = 0;
+    while (f < (int)h->filters.size() && h->filters[f].used) ++f;
+    if (f >= MHNSW_MAX_FILTERS) return fail(h, MHNSW_EUNSUPPORTED, "at most %d filters per index", MHNSW_MAX_FILTERS);
+    if (f == (int)h->filters.size()) h->filters.emplace_back();
+    h->filters[f].used = true;
+    h->filters_dirty = true;
+    if ((r = filters_fit(h)) || (r = filter_apply(h, f, keys, n, 1))) {
+        mhnsw_index::Filter& F = h->filters[f];
+        if (F.d) (void)hipFree(F.d);
+        F = mhnsw_index::Filter();
+        return r;
+    }
+    *out_filter = f;
+    return MHNSW_OK;
+}
+
+int mhnsw_filter_update(mhnsw_index* h, int filter, const int64_t* keys, int64_t n, int allow) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    if (n > 0 && !keys) return fail(h, MHNSW_EINVAL, "keys must be non-NULL");
+    int r = filter_slot(h, filter);
+    if (r || (r = drain(h)) || (r = filters_fit(h))) return r;
+    return filter_apply(h, filter, keys, n, allow);
+}
+
+int mhnsw_filter_count(mhnsw_index* h, int filter, int64_t* rows) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    if (!rows) return fail(h, MHNSW_EINVAL, "rows must be non-NULL");
+    if (int r = filter_slot(h, filter)) return r;
+    const mhnsw_index::Filter& F = h->filters[filter];
+    int64_t c = 0;
+    for (int64_t i = 0; i < h->n && (size_t)(i >> 5) < F.bits.size(); ++i)
+        c += ((F.bits[(size_t)i >> 5] >> (i & 31)) & 1u) && !h->hdead[i];
+    *rows = c;
+    return MHNSW_OK;
+}
+
+int mhnsw_filter_destroy(mhnsw_index* h, int filter) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    int r = filter_slot(h, filter);
+    if (r || (r = drain(h))) return r;
+    mhnsw_index::Filter& F = h->filters[filter];
+    if (F.d) (void)hipFree(F.d);
+    F = mhnsw_index::Filter();
+    h->filters_dirty = true;
+    return MHNSW_OK;
+}
+
+int mhnsw_search_filtered(mhnsw_index* h, const float* queries, int64_t B, int dim, int k, int ef, int route,
+                          const int32_t* filter_of, int64_t* out_keys, float* out_dist, int32_t* out_n) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    return search_filtered_impl(h, queries, false, B, dim, k, ef, route, filter_of, out_keys, out_dist, out_n, h->stream,
+                                false);
+}
+
+int mhnsw_search_filtered_device(mhnsw_index* h, const float* d_queries, int64_t B, int dim, int k, int ef, int route,
+                                 const int32_t* d_filter_of, int64_t* d_keys, float* d_dist, int32_t* d_n,
+                                 void* stream) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    return search_filtered_impl(h, d_queries, true, B, dim, k, ef, route, d_filter_of, d_keys, d_dist, d_n,
+                                (hipStream_t)stream, true);
 }
 
 // read-locked like the reference's Len/Dims (graph.go:421,829): a concurrent Add may grow h->layers

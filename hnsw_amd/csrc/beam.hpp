@@ -4,7 +4,8 @@
 // modes x 10 configurations compile in parallel).  One body, beam_query, runs
 // a query over either list: BList<R> in registers (k_search_beam,
 // k_search_beam_mw), or past them (max(ef, k) > 512) LList in LDS
-// (k_search_beam_lds).
+// (k_search_beam_lds).  The filtered search (k_search_beam_filt) is the same
+// body with the RowFilter policy over the LDS list.
 #pragma once
 #include <type_traits>
 
@@ -21,6 +22,8 @@ template <int L, int V, int XW>
 int launch_beam_cfg(const SearchArgs& a, hipStream_t s);
 template <int L, int V, int XW>
 int launch_beam_lds_cfg(const SearchArgs& a, hipStream_t s);
+template <int L, int V>
+int launch_beam_filt_cfg(const SearchArgs& a, const FilterArgs& f, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // batched search: one wave per query
@@ -145,6 +148,41 @@ __device__ __forceinline__ void beam_pad_out(const SearchArgs& a, int64_t b, int
 template <class LT>
 using BeamArgs = std::conditional_t<bl_regs<LT> == 0, const SearchArgs, const SearchArgs&>;
 
+// The filtered query (k_search_beam_filt): beam_query's descent, the layer-0 body
+// with the RowFilter policy, and the first k entries of its list R, which holds
+// allowed live rows only.  The plain beam_query below stays a function of its own,
+// word for word what it was: written as one template over the policy (or with a
+// forwarding overload, which copies `a` once more for the LDS list), it changed
+// the schedule of every LDS kernel and of the register kernels at 2 / 4 entries
+// per step (profiles/filtered_search_build.txt); the layer-0 body is shared.
+template <class C, class LT, int G, bool SCREEN, int XW, class BEv, class Flt>
+__device__ __forceinline__ void beam_query_f(BeamArgs<LT> a, int64_t b, const QReg<C>& q, float qn, uint32_t* smem,
+                                             WaveStats& st, const BEv& bev, Flt& flt) {
+    static_assert(Flt::on, "the plain search is beam_query");
+    const int lane = lane_id();
+    const int vsz = a.vis16 ? -1 : a.vis_n;  // (beam_layer: < 0 selects the compact set)
+    const uint32_t ep = beam_descend<C, G, SCREEN>(a, q, qn, smem, vsz, st, bev, beam_entry_of(a, b),
+                                                   beam_entry_layer(a), 1, true);
+    LT L;
+    const int efl = beam_efl(a);
+    float* mrg = bl_place(L, smem + beam_lds<LT>(a).list, efl);
+    beam_layer_l<C, LT, G, false, SCREEN, XW, bl_merges<LT>, BEv>(a.g, 0, ep, efl, q, qn, L, smem, vsz, st, bev, mrg, flt);
+    int nvalid = 0;
+#pragma unroll
+    for (int c = 0; c < bl_span(flt.R); c += 64) {
+        const uint32_t id = bl_chunk_id(flt.R, c);
+        const int pos = c + lane;  // (R is sorted and dense from entry 0)
+        const bool ok = id != EMPTY_ID;
+        if (ok && pos < a.k) {
+            a.out_keys[b * a.k + pos] = a.g.keys[id];
+            a.out_dist[b * a.k + pos] = bl_chunk_dist(flt.R, c);
+            if (a.out_ids) a.out_ids[b * a.k + pos] = (int32_t)id;
+        }
+        nvalid += __popcll(__ballot(ok));
+    }
+    beam_pad_out(a, b, min(nvalid, a.k));
+}
+
 // One query b over list LT: the greedy descent, the layer-0 beam, and its
 // first k live entries into the outputs.  BEv scores each batch of candidates
 // (beam_layer_l).
@@ -156,9 +194,10 @@ __device__ __forceinline__ void beam_query(BeamArgs<LT> a, int64_t b, const QReg
     const uint32_t ep = beam_descend<C, G, SCREEN>(a, q, qn, smem, vsz, st, bev, beam_entry_of(a, b),
                                                    beam_entry_layer(a), 1, true);
     LT L;
+    NoFilter nf;
     const int efl = beam_efl(a);
     float* mrg = bl_place(L, smem + beam_lds<LT>(a).list, efl);
-    beam_layer_l<C, LT, G, false, SCREEN, XW, bl_merges<LT>, BEv>(a.g, 0, ep, efl, q, qn, L, smem, vsz, st, bev, mrg);
+    beam_layer_l<C, LT, G, false, SCREEN, XW, bl_merges<LT>, BEv>(a.g, 0, ep, efl, q, qn, L, smem, vsz, st, bev, mrg, nf);
     // compact the sorted list into the first k live entries (deleted rows
     // route the search but are never returned)
     int nvalid = 0;
@@ -328,6 +367,38 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_search_be
     beam_wave<C, LList, G, SCREEN, XW>(a, b, smem);
 }
 
+// ---------------------------------------------------------------------------
+// filtered search (max(ef, k) <= 128, route width max(ef, k) <= a.ef <= LL_MAX_EF;
+// DESIGN.md "Filtered search"): k_search_beam_lds's wave with the RowFilter
+// policy.  a.ef is the ROUTE width (the LDS list's), f.ef the result width; the
+// fused launch only, one entry expanded per step.
+// ---------------------------------------------------------------------------
+template <class C, int G, bool SCREEN>
+__global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_search_beam_filt(SearchArgs a, FilterArgs f) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const int64_t b = blockIdx.x;
+    if (b >= a.B) return;
+    RowFilter flt;
+    flt.E = f.ef;
+    flt.bits = nullptr;
+    const int32_t fi = uni(f.filter_of[b]);
+    if (fi != -1) {  // (-1: every live row)
+        const uint32_t* bits = fi >= 0 && fi < f.nslots ? f.filters[fi] : nullptr;
+        if (!bits) {  // names no filter: no results, reported like the other device errors
+            if (lane_id() == 0) atomicOr(a.err, 8);
+            beam_pad_out(a, b, 0);
+            return;
+        }
+        flt.bits = bits;
+    }
+    QReg<C> q;
+    load_query(q, a.q + (size_t)b * C::PITCH);
+    const float qn = query_norm(q);
+    WaveStats st;
+    beam_query_f<C, LList, G, SCREEN, 1>(a, b, q, qn, smem, st, WaveBatch(), flt);
+    beam_stats(a, st);
+}
+
 // f(std::true_type / std::false_type): the kernels with and without the fp16 screen
 template <class F>
 int beam_with_screen(const SearchArgs& a, F&& f) {
@@ -389,6 +460,19 @@ template <int L, int V, int XW>
 int launch_beam_lds_cfg(const SearchArgs& a, hipStream_t s) {
     if (const int rc = beam_limits(a, true)) return rc;
     return launch_beam_t<Cfg<L, V>, LList, beam_group<L, V>(), XW>(a, s);
+}
+
+// the filtered launch: beam_limits over the route width
+template <int L, int V>
+int launch_beam_filt_cfg(const SearchArgs& a, const FilterArgs& f, hipStream_t s) {
+    if (f.ef < 1 || f.ef > 128 || a.k > f.ef || a.ef < f.ef) return -4;
+    if (const int rc = beam_limits(a, true)) return rc;
+    const int lds = beam_lds<LList>(a).words;
+    return beam_with_screen(a, [&](auto screen) {
+        hipLaunchKernelGGL((k_search_beam_filt<Cfg<L, V>, beam_group<L, V>(), decltype(screen)::value>),
+                           dim3((unsigned)a.B), dim3(64), (size_t)4 * (size_t)lds, s, a, f);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    });
 }
 
 // the ordered path's pre-pass (k_beam_descend); it fails as the layer-0 launch

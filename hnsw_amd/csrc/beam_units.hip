@@ -7,6 +7,7 @@
 //                          layer-0 step (search_expand), groups A B / C D
 //   beam_w1a/b .. w4a/b    k_search_beam_lds (the LDS-resident list, max(ef, k)
 //                          past the register lists), XW 1 / 2 / 4, groups A B / C D
+//   beam_fa, beam_fb       k_search_beam_filt (the filtered search), groups A B / C D
 //   beam_desc              k_beam_descend (the ordered path's descent pre-pass),
 //                          every configuration
 #include "beam.hpp"
@@ -21,6 +22,7 @@
 #define LDS1_(L, V, G) template int launch_beam_lds_cfg<L, V, 1>(const SearchArgs&, hipStream_t);
 #define LDS2_(L, V, G) template int launch_beam_lds_cfg<L, V, 2>(const SearchArgs&, hipStream_t);
 #define LDS4_(L, V, G) template int launch_beam_lds_cfg<L, V, 4>(const SearchArgs&, hipStream_t);
+#define FILT_(L, V, G) template int launch_beam_filt_cfg<L, V>(const SearchArgs&, const FilterArgs&, hipStream_t);
 #define DESC_(L, V, G) template int launch_beam_descend_cfg<L, V>(const SearchArgs&, hipStream_t);
 
 #define U_beam_a MH_CFGS_A(REG1_)
@@ -37,6 +39,8 @@
 #define U_beam_w2b MH_CFGS_C(LDS2_) MH_CFGS_D(LDS2_)
 #define U_beam_w4a MH_CFGS_A(LDS4_) MH_CFGS_B(LDS4_)
 #define U_beam_w4b MH_CFGS_C(LDS4_) MH_CFGS_D(LDS4_)
+#define U_beam_fa MH_CFGS_A(FILT_) MH_CFGS_B(FILT_)
+#define U_beam_fb MH_CFGS_C(FILT_) MH_CFGS_D(FILT_)
 #define U_beam_desc MH_FOR_EACH_CFG(DESC_)
 
 #define MH_UNIT_CAT2(a, b) a##b

@@ -532,6 +532,11 @@ __device__ __forceinline__ uint32_t bl_next(LList& L) {
     return EMPTY_ID;
 }
 
+// the distance of the entry the last bl_next picked (it returned that entry's id)
+__device__ __forceinline__ float bl_picked_dist(const LList& L) {
+    return __int_as_float(uni(__float_as_int(L.d[L.nx - 1])));
+}
+
 // bl_merge over the LDS list: the k <= 64 candidates of L.cb, each ranked among
 // the candidates and (binary search over L.d[0, ef], which can reach ef: see
 // bl_merge) in the list.  The list's entries move up in place by the number of
@@ -691,6 +696,32 @@ struct WaveBatch {
 };
 
 // ---------------------------------------------------------------------------
+// The layer-0 filter policy of beam_layer_l (DESIGN.md "Filtered search").
+// NoFilter: the plain search, nothing added.  RowFilter: a second sorted list
+// R (registers, capacity E <= 128) of the rows met that the query's allow-list
+// holds and that are not deleted.  The route list L keeps routing through
+// every row; a step offers a row to either list only when it beats both lists'
+// worst entries as they stood BEFORE the step, L keeps its best W and R its
+// best E of what was offered (so the arrival order inside a step is
+// immaterial), and the search stops at the first unexpanded entry that R's
+// worst entry precedes.  The result is R.
+// ---------------------------------------------------------------------------
+struct NoFilter {
+    static constexpr bool on = false;
+};
+struct RowFilter {
+    static constexpr bool on = true;
+    const uint32_t* bits;  // row id -> bit, 32 rows a word (nullptr: every live row)
+    int E;                 // R's capacity: max(ef, k) <= 128
+    BList<2> R;
+    // lane-parallel: is row id (< g.capn) in the allow-set
+    __device__ __forceinline__ bool allowed(const GraphDev& g, uint32_t id) const {
+        const bool bit = bits ? ((bits[id >> 5] >> (id & 31)) & 1u) != 0 : true;
+        return bit && !is_dead(g, id);
+    }
+};
+
+// ---------------------------------------------------------------------------
 // beam: sorted list of <= ef entries; stop when every entry is expanded
 // ---------------------------------------------------------------------------
 // XW: entries expanded per step.  1 is the standard best-first search (the
@@ -710,18 +741,30 @@ struct WaveBatch {
 // through bl_merge once per step, with `mrg` (BL_MERGE_WORDS of LDS) as its
 // scratch.
 // LT: the list, BList<R> (registers) or LList (LDS).
-template <class C, class LT, int G, bool COH, bool SCREEN, int XW, bool MERGE, class BEv>
+// Flt: the filter policy (NoFilter; RowFilter with the LDS list, XW 1 and MERGE,
+// where a step is one batch, so "before the step" is "before the batch").
+template <class C, class LT, int G, bool COH, bool SCREEN, int XW, bool MERGE, class BEv, class Flt>
 __device__ __forceinline__ void beam_layer_l(const GraphDev& g, int layer, uint32_t entry, int ef, const QReg<C>& q,
                                              float qn, LT& L, uint32_t* vis, int vsize, WaveStats& st, const BEv& bev,
-                                             float* mrg) {
+                                             float* mrg, Flt& flt) {
+    static_assert(!Flt::on || (XW == 1 && MERGE && bl_regs<LT> == 0), "the filter runs on the LDS list, one entry a step");
     const int lane = lane_id();
     bl_init(L);
+    if constexpr (Flt::on) bl_init(flt.R);
     if (entry == EMPTY_ID) return;
     vis_any_clear(vis, vsize);
     wave_sync();  // (the list and the visited set belong to this wave alone)
     if (lane == 0) vis_any_probe(vis, vsize, entry);
     int vcount = 1;
-    eval_list<C, G>(g, q, qn, entry, 1, g.metric, [&](float d, uint32_t u) { bl_insert(L, ef, d, u); });
+    if constexpr (Flt::on) {
+        const bool ok = flt.allowed(g, guard_id(g, entry));  // (uniform)
+        eval_list<C, G>(g, q, qn, entry, 1, g.metric, [&](float d, uint32_t u) {
+            bl_insert(L, ef, d, u);
+            if (ok) bl_insert(flt.R, flt.E, d, u);
+        });
+    } else {
+        eval_list<C, G>(g, q, qn, entry, 1, g.metric, [&](float d, uint32_t u) { bl_insert(L, ef, d, u); });
+    }
     st.E += 1;
     st.F += 1;
     const bool screen = SCREEN && h16_query_ok(qn);
@@ -749,6 +792,14 @@ __device__ __forceinline__ void beam_layer_l(const GraphDev& g, int layer, uint3
         uint32_t cur[XW];
         cur[0] = bl_next(L);
         if (cur[0] == EMPTY_ID) break;
+        float rwd = __int_as_float(0x7f800000);  // Flt: R's worst entry before the step
+        uint32_t rwi = EMPTY_ID;
+        if constexpr (Flt::on) {
+            bl_at(flt.R, flt.E - 1, rwd, rwi);
+            // R is full and its worst entry precedes the best unexpanded one:
+            // nothing left can improve the results
+            if (rwi != EMPTY_ID && lt_di(rwd, rwi, bl_picked_dist(L), cur[0] & ID_MASK)) break;
+        }
 #pragma unroll
         for (int w = 1; w < XW; ++w) cur[w] = bl_next(L);
         // the adjacency rows are loaded together with their degrees (rows are
@@ -769,17 +820,24 @@ __device__ __forceinline__ void beam_layer_l(const GraphDev& g, int layer, uint3
         }
         uint32_t cids[XW];
         int cnts[XW];
+        bool cok = false;  // Flt: lane t < cnts[0]: candidate t is in the allow-set
 #pragma unroll
         for (int w = 0; w < XW; ++w) {
             const bool have = lane < deg[w];
             uint32_t nb = have ? (uint32_t)rowv[w] : 0u;
             int pr = 0;
+            bool ok = false;
             if (have && nb != 0xFFFFFFFFu) {
                 nb = guard_id(g, nb);
+                if constexpr (Flt::on) ok = flt.allowed(g, nb);  // one gather a step, beside the probe
                 pr = vis_any_probe(vis, vsize, nb);
             }
             vcount += __popcll(__ballot(pr == 1));
             cids[w] = compact(nb, pr != 0, cnts[w]);
+            if constexpr (Flt::on) {
+                int c2;
+                cok = compact(ok ? 1u : 0u, pr != 0, c2) != 0 && lane < c2;
+            }
         }
         // the new neighbours of consecutive expanded entries share a batch while
         // they fit the wave
@@ -804,6 +862,9 @@ __device__ __forceinline__ void beam_layer_l(const GraphDev& g, int layer, uint3
         float wd = __int_as_float(0x7f800000);
         uint32_t wi = EMPTY_ID;
         if constexpr (SCREEN || MERGE) bl_at(L, ef - 1, wd, wi);  // the worst before the step: it only decreases during it
+        // Flt: the screen's threshold is the lower of the two lists' worst distances
+        // (what the copy proves worse than it is offered to neither list)
+        const float sd = Flt::on ? fminf(wd, rwd) : wd;
         int bk = 0;  // MERGE: the step's candidates below that worst, in mrg's buffer
         // the batches are taken from slot 0 and the slots shifted down, so every
         // register index is static whether or not the compiler unrolls this loop
@@ -826,6 +887,22 @@ __device__ __forceinline__ void beam_layer_l(const GraphDev& g, int layer, uint3
                         bk = 0;
                     }
                     float* cb = bl_cbuf(L, mrg);
+                    if constexpr (Flt::on) {
+                        // offered: below both worst entries as saved before the step (R's
+                        // live bound falls inside the step; the saved one decides)
+                        auto sink = [&](float d, uint32_t u) {
+                            if (lt_di(d, u, wd, wi & ID_MASK) && lt_di(d, u, rwd, rwi)) {
+                                if (lane == 0) {
+                                    cb[bk] = d;
+                                    reinterpret_cast<uint32_t*>(cb)[64 + bk] = u;
+                                }
+                                ++bk;
+                                if (__ballot(lane < cnt && cid == u && cok) != 0) bl_insert(flt.R, flt.E, d, u);
+                            }
+                        };
+                        st.F += bev.template score<C, G, SCREEN>(g, q, qn, cid, cnt, sd, screen, margin, sink, st.S);
+                        continue;
+                    }
                     auto sink = [&](float d, uint32_t u) {
                         if (lt_di(d, u, wd, wi & ID_MASK)) {
                             if (lane == 0) {
@@ -876,7 +953,8 @@ template <class C, int R, int G, bool COH = false, bool SCREEN = false, int XW =
 __device__ __forceinline__ void beam_layer(const GraphDev& g, int layer, uint32_t entry, int ef, const QReg<C>& q, float qn,
                            BList<R>& L, uint32_t* vis, int vsize, WaveStats& st, const BEv& bev = BEv(),
                            float* mrg = nullptr) {
-    beam_layer_l<C, BList<R>, G, COH, SCREEN, XW, MERGE, BEv>(g, layer, entry, ef, q, qn, L, vis, vsize, st, bev, mrg);
+    NoFilter nf;
+    beam_layer_l<C, BList<R>, G, COH, SCREEN, XW, MERGE, BEv>(g, layer, entry, ef, q, qn, L, vis, vsize, st, bev, mrg, nf);
 }
 
 // ---------------------------------------------------------------------------

@@ -89,6 +89,16 @@ struct SearchArgs {
     int64_t order_chunk = 0;             // > 0: workgroup i takes position (i % 8) * chunk + i / 8; 0: position i
 };
 
+// Filtered beam search (beam.hpp k_search_beam_filt): the second kernel
+// argument.  With it SearchArgs::ef is the route width W (the layer-0 list the
+// search routes through, in LDS) and `ef` here the result width max(ef, k).
+struct FilterArgs {
+    const uint32_t* const* filters;  // [nslots] a filter's bitmap, row id -> bit (nullptr: no such filter)
+    int nslots;
+    int ef;                          // max(ef, k) <= 128
+    const int32_t* filter_of;        // [B] query b's filter (-1: every live row)
+};
+
 // the launch that runs one workgroup of 4 waves per query (beam.hpp
 // k_search_beam_mw): small batches of the standard search on the narrow lists
 inline bool beam_small_batch(const SearchArgs& a) {
@@ -127,6 +137,7 @@ int launch_sweep(const float* q, const float* X, int64_t n, int pitch, int lpr, 
                  hipStream_t s);
 int launch_sweep_raw(const float* q, const float* X, int64_t n, int dim, int metric, float* out, hipStream_t s);
 int launch_search_beam(const SearchArgs& a, int lpr, int vpl, hipStream_t s);
+int launch_search_beam_filtered(const SearchArgs& a, const FilterArgs& f, int lpr, int vpl, hipStream_t s);
 // ordered path: the descent pre-pass (writes a.ep0 / a.okey / a.oidx, adds its
 // counters to a.stats), then the sort of the keys into the permutation (order.hip)
 int launch_beam_descend(const SearchArgs& a, int lpr, int vpl, hipStream_t s);

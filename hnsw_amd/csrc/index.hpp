@@ -212,6 +212,19 @@ struct mhnsw_index {
     std::vector<int32_t> hprev;                      // kprev mirror (aliased only)
     std::unordered_map<int64_t, int32_t> dead_kid;   // deleted keys -> kid, for a later re-add
     int64_t stats_host[8] = {0};
+    // filtered search: per-query allow-lists (mhnsw_filter_*), slot = filter id.
+    // A bitmap is row id -> bit over the row capacity; it grows zero-filled with
+    // the rows (filters_fit), and Import / Load drop every filter (the ids change).
+    struct Filter {
+        bool used = false;
+        std::vector<uint32_t> bits;  // host mirror, the words the device bitmap holds
+        uint32_t* d = nullptr;
+    };
+    std::vector<Filter> filters;
+    const uint32_t** d_filters = nullptr;  // [MHNSW_MAX_FILTERS] device table of the bitmaps (nullptr: none)
+    bool filters_dirty = false;            // the table is to be uploaded
+    int filter_route = 1024;               // route width of a filtered search that names none
+    DevBuf<int32_t> fof;                   // a host-pointer filtered search's filter_of
     std::string err;
     mutable std::shared_mutex mu;
 };
@@ -270,6 +283,10 @@ int search_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B,
 int order_meta(mhnsw_index* h, hipStream_t s);
 int search_body(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int mode, int ef, const int64_t* entry_key, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool timing, int32_t* out_ids, bool sticky);
 void reset_graph(mhnsw_index* h);
+constexpr int MHNSW_MAX_FILTERS = 1024;
+void drop_filters(mhnsw_index* h);
+int filters_fit(mhnsw_index* h);
+int search_filtered_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int ef, int route, const int32_t* filter_of, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool sticky);
 int import_csr(mhnsw_index* h, int64_t N, int dim, int L, int cap, const int64_t* keys, const float* vecs, const int32_t* deg, const int32_t* adj, const int32_t* entry, const uint8_t* dead);
 const char* metric_name(int m);
 int strkey_relabel(mhnsw_index* h);

@@ -52,11 +52,13 @@ void reset_graph(mhnsw_index* h) {
     h->l2s.clear();
     h->partial_rows = 0;
     h->xgone_epoch = ~0ull;
+    drop_filters(h);
 }
 
 int import_csr(mhnsw_index* h, int64_t N, int dim, int L, int cap, const int64_t* keys, const float* vecs,
                const int32_t* deg, const int32_t* adj, const int32_t* entry, const uint8_t* dead) {
     if (h->n > 0) return fail(h, MHNSW_EINVAL, "import requires an empty index");
+    drop_filters(h);  // (the row ids are the import's from here on)
     if (L > MH_MAXL) return fail(h, MHNSW_EUNSUPPORTED, "more than %d layers", MH_MAXL);
     if (cap > 64) return fail(h, MHNSW_EUNSUPPORTED, "degree cap above 64 unsupported");
     int r;

@@ -18,6 +18,7 @@ namespace mh {
     extern template int launch_beam_lds_cfg<L, V, 2>(const SearchArgs&, hipStream_t); \
     extern template int launch_beam_lds_cfg<L, V, 4>(const SearchArgs&, hipStream_t); \
     extern template int launch_beam_descend_cfg<L, V>(const SearchArgs&, hipStream_t); \
+    extern template int launch_beam_filt_cfg<L, V>(const SearchArgs&, const FilterArgs&, hipStream_t); \
     extern template int launch_compat_cfg<L, V>(const SearchArgs&, hipStream_t);     \
     extern template int launch_negatives_cfg<L, V>(const NegArgs&, hipStream_t);
 MH_FOR_EACH_CFG(X_)
@@ -421,6 +422,11 @@ int launch_search_beam(const SearchArgs& a, int lpr, int vpl, hipStream_t s) {
             return lds ? launch_beam_lds_cfg<c.L, c.V, xw.value>(a, s) : launch_beam_cfg<c.L, c.V, xw.value>(a, s);
         });
     });
+}
+
+int launch_search_beam_filtered(const SearchArgs& a, const FilterArgs& f, int lpr, int vpl, hipStream_t s) {
+    if (a.B <= 0) return 0;
+    return with_cfg(lpr, vpl, [&](auto c) { return launch_beam_filt_cfg<c.L, c.V>(a, f, s); });
 }
 
 int launch_beam_descend(const SearchArgs& a, int lpr, int vpl, hipStream_t s) {

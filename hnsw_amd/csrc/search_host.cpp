@@ -492,6 +492,141 @@ int search_body(mhnsw_index* h, const float* queries, bool on_device, int64_t B,
     return 0;
 }
 
+// The filtered beam search (beam.hpp k_search_beam_filt): the fused launch over
+// the LDS list of `route` entries, results from the list of max(ef, k) allowed
+// rows.  Stream ordering, scratch and the error words as search_impl's.
+static int search_filtered_body(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int ef,
+                                int route, const int32_t* filter_of, int64_t* okeys, float* odist, int32_t* on,
+                                hipStream_t s, bool sticky) {
+    int r = validate(h);
+    if (r) return r;
+    if (k <= 0) return fail(h, MHNSW_EK, "k must be greater than 0, got %d", k);
+    if (h->layers_exist && h->dim != dim) {
+        if (B == 1) return fail(h, MHNSW_EDIM, "embedding dimension mismatch: %d != %d", h->dim, dim);
+        return fail(h, MHNSW_EDIM, "embedding dimension mismatch for query %d: %d != %d", 0, h->dim, dim);
+    }
+    if (h->build_mode == MHNSW_BUILD_FLAT)
+        return fail(h, MHNSW_EUNSUPPORTED, "flat index (build_mode 2) supports exact search only");
+    if (ef <= 0) ef = h->ef;
+    const int E = std::max(ef, k);
+    if (E > 128) return fail(h, MHNSW_EUNSUPPORTED, "filtered search supports max(ef,k) <= 128");
+    if (route <= 0) route = h->filter_route;
+    const int W = std::max(route, E);
+    if (W > 2048) return fail(h, MHNSW_EUNSUPPORTED, "filtered search supports route <= 2048");  // (LL_MAX_EF)
+    if (B <= 0) return 0;
+    if (!filter_of) return fail(h, MHNSW_EINVAL, "filter_of must be non-NULL");
+    if (!on_device)
+        for (int64_t b = 0; b < B; ++b) {
+            const int32_t f = filter_of[b];
+            if (f < -1 || (f >= 0 && (f >= (int)h->filters.size() || !h->filters[f].used)))
+                return fail(h, MHNSW_EINVAL, "unknown filter %d", f);
+        }
+    if (!h->layers_exist || live_count(h) == 0) {
+        if (on_device)
+            HIPCHK(h, hipMemsetAsync(on, 0, B * 4, s));
+        else
+            memset(on, 0, B * 4);
+        return 0;
+    }
+    // a bitmap that has to grow with the rows moves: nothing enqueued may read it
+    const size_t words = (size_t)((h->capn + 31) / 32);
+    for (const auto& F : h->filters)
+        if (F.used && F.bits.size() < words) {
+            if ((r = drain(h))) return r;
+            break;
+        }
+    if ((r = filters_fit(h))) return r;
+    const int top = top_live_layer(h);
+    if ((r = ensure_buf(h, h->qpad, (size_t)B * h->pitch))) return r;
+    const float* qsrc = queries;
+    const int32_t* dfof = filter_of;
+    if (!on_device) {
+        if ((r = ensure_buf(h, h->tmp, (size_t)B * dim)) || (r = ensure_buf(h, h->fof, (size_t)B))) return r;
+        HIPCHK(h, hipMemcpyAsync(h->tmp.p, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->fof.p, filter_of, (size_t)B * 4, hipMemcpyHostToDevice, s));
+        qsrc = h->tmp.p;
+        dfof = h->fof.p;
+    }
+    LCHK(h, launch_pad_rows(qsrc, B, dim, h->qpad.p, h->pitch, s));
+    int64_t* dk = okeys;
+    float* dd = odist;
+    int32_t* dn = on;
+    if (!on_device) {
+        if ((r = ensure_buf(h, h->okeys, (size_t)B * k)) || (r = ensure_buf(h, h->odist, (size_t)B * k)) ||
+            (r = ensure_buf(h, h->on, (size_t)B)))
+            return r;
+        dk = h->okeys.p;
+        dd = h->odist.p;
+        dn = h->on.p;
+    }
+    int* errw = sticky ? h->d_err + 1 : h->d_err;
+    if (!sticky) HIPCHK(h, hipMemsetAsync(h->d_err, 0, sizeof(int), s));
+    if ((r = sync_layer_entries(h))) return r;
+    if ((r = sync_layer_table(h)) || (r = order_meta(h, s))) return r;
+    SearchArgs a;
+    a.g = graph_view(h);
+    a.g.err = errw;
+    a.q = h->qpad.p;
+    a.B = B;
+    a.k = k;
+    a.ef = W;  // (the route list's width: FilterArgs::ef is the result list's)
+    a.top = top;
+    a.entry = (uint32_t)h->layers[top].entry;
+    a.layer_entry = h->d_layer_entry;
+    a.out_keys = dk;
+    a.out_dist = dd;
+    a.out_n = dn;
+    a.out_ids = nullptr;
+    a.stats = h->d_stats;
+    a.err = errw;
+    a.vis_log2 = h->vis_log2;
+    a.vis_n = beam_vis_entries(h);
+    // the visited set as the LDS-list tier's at max(ef, k) = W (search_body)
+    a.vis16 = h->vis_compact && W > 128 && h->capn <= (int64_t(1) << 24) && (int64_t)a.vis_n >= (int64_t)VIS16_WORDS &&
+              a.vis_n < VIS16_HOMES;
+    if (!a.vis16 && h->vis_entries <= 0) a.vis_n = std::max(a.vis_n, 4 * W);
+    a.upper_ef = h->upper_ef;
+    a.mw_max_b = 0;
+    a.expand = 1;
+    FilterArgs f;
+    f.filters = h->d_filters;
+    f.nslots = MHNSW_MAX_FILTERS;
+    f.ef = E;
+    f.filter_of = dfof;
+    HIPCHK(h, hipEventRecord(h->ev0, s));
+    const int lr = launch_search_beam_filtered(a, f, h->lpr, h->vpl, s);
+    if (lr == -2)
+        return fail(h, MHNSW_EUNSUPPORTED, "filtered search LDS budget exceeded (route=%d, vis_entries=%d)", W, a.vis_n);
+    LCHK(h, lr);
+    HIPCHK(h, hipEventRecord(h->ev1, s));
+    h->have_timing = true;
+    h->have_gemm_timing = false;
+    h->stats_host[6] += B;
+    if (!on_device) {
+        HIPCHK(h, hipMemcpyAsync(okeys, dk, (size_t)B * k * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(odist, dd, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(on, dn, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+        int err = 0;
+        HIPCHK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        if (err & 4) return fail(h, MHNSW_EINTERNAL, "out-of-range node id in adjacency (graph corrupt)");
+        if (err & 8) return fail(h, MHNSW_EINVAL, "unknown filter in filter_of");
+        if (err) return fail(h, MHNSW_EINTERNAL, "visited set overflow (raise vis_log2)");
+    }
+    return 0;
+}
+
+int search_filtered_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int ef, int route,
+                         const int32_t* filter_of, int64_t* okeys, float* odist, int32_t* on, hipStream_t s,
+                         bool sticky) {
+    if (h->scr_valid && h->scr_stream != s) HIPCHK(h, hipStreamWaitEvent(s, h->scr_ev, 0));
+    const int r = search_filtered_body(h, queries, on_device, B, dim, k, ef, route, filter_of, okeys, odist, on, s, sticky);
+    HIPCHK(h, hipEventRecord(h->scr_ev, s));
+    h->scr_stream = s;
+    h->scr_valid = true;
+    return r;
+}
+
 }  // namespace mhh
 
 extern "C" {

@@ -182,6 +182,46 @@ class SplitMix64Rand:
 DOG_QUERY_HACK = 1  # Graph.TestHacks bit: graph.go:563-569, 595-619
 
 
+class Filter:
+    """A device-resident allow-list of a Graph's rows (Graph.Filter).  Keys are
+    the graph's Go keys, encoded like every other key (strings included)."""
+
+    def __init__(self, graph: "Graph", keys=()):
+        self._g = graph
+        self.id = self._was = None
+        imgs = np.ascontiguousarray(graph.encode_keys(list(keys)), np.int64)
+        out = C.c_int()
+        graph._check(load().mhnsw_filter_create(graph._h, _ptr(imgs, C.c_int64), len(imgs), C.byref(out)))
+        self.id = self._was = out.value
+
+    def _fid(self) -> int:
+        if self.id is None:  # closed: the engine may have given the slot to another filter
+            raise HnswError(-1, f"unknown filter {self._was}")
+        return self.id
+
+    def _update(self, keys, allow: int):
+        g = self._g
+        imgs = np.ascontiguousarray(g.encode_keys(list(keys)), np.int64)
+        g._check(load().mhnsw_filter_update(g._h, self._fid(), _ptr(imgs, C.c_int64), len(imgs), allow))
+
+    def add(self, keys):
+        self._update(keys, 1)
+
+    def remove(self, keys):
+        self._update(keys, 0)
+
+    def count(self) -> int:
+        """The allowed rows that are live."""
+        n = C.c_int64()
+        self._g._check(load().mhnsw_filter_count(self._g._h, self._fid(), C.byref(n)))
+        return n.value
+
+    def close(self):
+        fid, self.id = self.id, None  # (closed whatever the engine answers: an Import has dropped it already)
+        if fid is not None and getattr(self._g, "_h", None):
+            self._g._check(load().mhnsw_filter_destroy(self._g._h, fid))
+
+
 class Graph:
     """graph.go:305-332 Graph[K].  Public fields M, Ml, EfSearch, Distance and
     Rng are read by every call, like the Go struct fields.  Rng is either a
@@ -485,6 +525,57 @@ class Graph:
         """Wait for the last enqueued search_device and raise what its kernels
         reported (compat visited-set overflow, out-of-range ids); clears it."""
         self._check(load().mhnsw_device_status(self._h))
+
+    # -- filtered search (the reference's facets extension, in the layer-0 walk) ------
+    def Filter(self, keys=()) -> "Filter":
+        """An allow-list of the live rows of `keys` (absent keys are ignored);
+        rows added later are not allowed until `add` names their keys."""
+        return Filter(self, keys)
+
+    def _filter_ids(self, filters, B: int) -> np.ndarray:
+        if isinstance(filters, Filter) or filters is None:
+            filters = [filters] * B
+        filters = list(filters)
+        if len(filters) != B:
+            raise HnswError(-1, f"{len(filters)} filters for {B} queries")
+        for f in filters:
+            if f is not None and (not isinstance(f, Filter) or f._g is not self):
+                raise HnswError(-1, "filter of another graph")
+        return np.asarray([-1 if f is None else f._fid() for f in filters], np.int32)
+
+    def search_filtered_arrays(self, queries, k: int, filters, ef: int = 0, route: int = 0):
+        """Beam search among the allowed rows -> (keys int64[B,k], dist
+        float32[B,k], n int32[B]).  filters: one Filter, or one per query (None:
+        every live row).  The search routes through a list of `route` entries
+        (0: option filter_route) and keeps the max(ef, k) <= 128 best allowed
+        rows; a route too narrow for the filter returns fewer than k."""
+        self._sync()
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        B, d = q.shape
+        fo = np.ascontiguousarray(self._filter_ids(filters, B))
+        kk = max(int(k), 1)
+        ok = np.zeros((B, kk), np.int64)
+        od = np.zeros((B, kk), np.float32)
+        on = np.zeros(B, np.int32)
+        self._check(load().mhnsw_search_filtered(self._h, _ptr(q, C.c_float), B, d, int(k), int(ef), int(route),
+                                                 _ptr(fo, C.c_int32), _ptr(ok, C.c_int64), _ptr(od, C.c_float),
+                                                 _ptr(on, C.c_int32)))
+        return ok, od, on
+
+    def search_filtered_device(self, q_ptr: int, B: int, dim: int, k: int, filter_of_ptr: int, keys_ptr: int,
+                               dist_ptr: int, n_ptr: int, ef: int = 0, route: int = 0, stream: int = 0):
+        """search_filtered_arrays on device buffers (filter_of: int32[B] filter
+        ids, -1 every live row), enqueued on `stream` (no host sync)."""
+        self._check(load().mhnsw_search_filtered_device(self._h, C.c_void_p(q_ptr), B, dim, k, ef, route,
+                                                        C.c_void_p(filter_of_ptr), C.c_void_p(keys_ptr),
+                                                        C.c_void_p(dist_ptr), C.c_void_p(n_ptr), C.c_void_p(stream)))
+
+    def SearchFiltered(self, near, k: int, filter, ef: int = 0, route: int = 0) -> List[Node]:
+        q = np.asarray(near, np.float32).reshape(1, -1)
+        ok, _, on = self.search_filtered_arrays(q, k, filter, ef=ef, route=route)
+        return self._nodes(ok[0, : on[0]])
 
     def _node(self, key) -> Node:
         v = self._values.get(key)

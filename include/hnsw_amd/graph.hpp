@@ -348,6 +348,73 @@ class Graph {  // graph.go:305-332
         return {out, {}};
     }
 
+    // Filtered search (mhnsw.h "Filtered search"): an allow-list of the live
+    // rows of some keys, owned by the graph's handle and released with this
+    // object.  The graph must outlive its filters.
+    class Filter {
+       public:
+        Filter(Graph& g, const std::vector<K>& keys) : g_(&g) {
+            const std::vector<int64_t> im = Codec::encode(g.h_, keys, false);
+            err_ = make_error(mhnsw_filter_create(g.h_, im.data(), (int64_t)im.size(), &id_), g.h_);
+            if (err_) id_ = -1;
+        }
+        Filter(const Filter&) = delete;
+        Filter& operator=(const Filter&) = delete;
+        Filter(Filter&& o) noexcept : g_(o.g_), id_(o.id_), err_(std::move(o.err_)) { o.id_ = -1; }
+        ~Filter() { Close(); }
+
+        const Error& Err() const { return err_; }  // of the constructor
+        int Id() const { return id_; }
+        const Graph* Owner() const { return g_; }
+        Error Add(const std::vector<K>& keys) { return update(keys, 1); }
+        Error Remove(const std::vector<K>& keys) { return update(keys, 0); }
+        std::pair<int64_t, Error> Count() const {
+            int64_t n = 0;
+            const int rc = mhnsw_filter_count(g_->h_, id_, &n);
+            return {n, make_error(rc, g_->h_)};
+        }
+        void Close() {
+            if (id_ >= 0) mhnsw_filter_destroy(g_->h_, id_);
+            id_ = -1;
+        }
+
+       private:
+        Error update(const std::vector<K>& keys, int allow) {
+            const std::vector<int64_t> im = Codec::encode(g_->h_, keys, false);
+            return make_error(mhnsw_filter_update(g_->h_, id_, im.data(), (int64_t)im.size(), allow), g_->h_);
+        }
+        Graph* g_;
+        int id_ = -1;
+        Error err_;
+    };
+    Filter MakeFilter(const std::vector<K>& keys) { return Filter(*this, keys); }
+
+    // the k nearest rows of `filter` (nullptr: every live row); ef <= 0:
+    // EfSearch, route <= 0: the option filter_route
+    std::pair<std::vector<Node<K>>, Error> SearchFiltered(const Vector& near, int k, const Filter* filter, int ef = 0,
+                                                          int route = 0) {
+        sync();
+        const int have = Dims();
+        if (have && (int)near.size() != have)
+            return {{}, Error{"embedding dimension mismatch: " + std::to_string(have) + " != " +
+                                  std::to_string(near.size()),
+                              MHNSW_EDIM}};
+        const size_t kk = k > 0 ? (size_t)k : 1;
+        std::vector<int64_t> keys(kk);
+        std::vector<float> dist(kk);
+        int32_t n = 0;
+        if (filter && filter->Owner() != this) return {{}, Error{"filter of another graph", MHNSW_EINVAL}};
+        if (filter && filter->Id() < 0) return {{}, Error{"unknown filter -1", MHNSW_EINVAL}};  // closed, or never made
+        const int32_t fo = filter ? filter->Id() : -1;
+        const int rc = mhnsw_search_filtered(h_, near.data(), 1, (int)near.size(), k, ef, route, &fo, keys.data(),
+                                             dist.data(), &n);
+        if (rc < 0) return {{}, make_error(rc, h_)};
+        std::vector<Node<K>> out;
+        const std::vector<K> ks = Codec::decode(h_, keys.data(), (size_t)n);
+        for (const K& key : ks) out.push_back(Node<K>{key, lookup_value(key)});
+        return {out, {}};
+    }
+
     int Len() const { return (int)mhnsw_len(h_); }   // graph.go:829
     int Dims() const { return mhnsw_dims(h_); }      // graph.go:421
 

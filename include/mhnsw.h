@@ -217,6 +217,40 @@ int mhnsw_search_device(mhnsw_index *h, const float *d_queries, int64_t B, int d
  * clears the word. */
 int mhnsw_device_status(mhnsw_index *h);
 
+/* ---- Filtered search (the reference's hnsw-extensions/facets, search.go:15-88,
+ * with the predicate applied inside the layer-0 walk; DESIGN.md "Filtered
+ * search") ----
+ * A filter is an allow-list of rows owned by the handle: a bitmap over its row
+ * capacity.  mhnsw_filter_create allows the live layer-0 rows of `keys` (absent
+ * keys are ignored) and returns the filter's id; mhnsw_filter_update allows
+ * (allow != 0) or disallows the rows of `keys`.  Rows added later are not
+ * allowed until an update names their keys.  mhnsw_filter_count: the allowed
+ * rows that are live.  At most 1024 filters per handle.  Import / Load drop
+ * every filter (the row ids change): its id then fails with MHNSW_EINVAL,
+ * "unknown filter %d". */
+int mhnsw_filter_create(mhnsw_index *h, const int64_t *keys, int64_t n, int *out_filter);
+int mhnsw_filter_update(mhnsw_index *h, int filter, const int64_t *keys, int64_t n, int allow);
+int mhnsw_filter_count(mhnsw_index *h, int filter, int64_t *rows);
+int mhnsw_filter_destroy(mhnsw_index *h, int filter);
+/* The beam search among the allowed rows: query b returns its nearest rows of
+ * filter filter_of[b] (-1: every live row).  The search routes through every
+ * row in a list of `route` entries and collects the allowed ones in a list of
+ * max(ef, k) <= 128 entries; it stops when no unexpanded entry can improve
+ * that list.  ef <= 0 uses EfSearch; route <= 0 uses the option filter_route
+ * (default 1024); a route below max(ef, k) is raised to it; route <= 2048.
+ * With every row allowed the result is mhnsw_search's in MHNSW_MODE_BEAM at the
+ * same ef, whatever the route.  A route too narrow for the filter's
+ * selectivity returns fewer than k rows (no error).  Errors: MHNSW_EUNSUPPORTED
+ * "filtered search supports max(ef,k) <= 128" / "filtered search supports
+ * route <= 2048"; MHNSW_EINVAL for a filter_of entry that names no filter (the
+ * *_device call, whose filter_of is a device pointer, reports it through
+ * mhnsw_device_status). */
+int mhnsw_search_filtered(mhnsw_index *h, const float *queries, int64_t B, int dim, int k, int ef, int route,
+                          const int32_t *filter_of, int64_t *out_keys, float *out_dist, int32_t *out_n);
+int mhnsw_search_filtered_device(mhnsw_index *h, const float *d_queries, int64_t B, int dim, int k, int ef, int route,
+                                 const int32_t *d_filter_of, int64_t *d_keys, float *d_dist, int32_t *d_n,
+                                 void *stream);
+
 /* ---- SearchWithNegative(s) / BatchSearchWithNegatives (graph.go:1116-1537) ----
  * Query b's negatives are the next neg_count[b] rows of `negatives` (B*dim
  * queries, sum(neg_count)*dim negatives).  Candidates = Search(near,
