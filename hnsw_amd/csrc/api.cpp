@@ -1455,11 +1455,8 @@ int mhnsw_device_status(mhnsw_index* h) {
     if (h->scr_valid) HIPCHK(h, hipEventSynchronize(h->scr_ev));
     int err = 0;
     HIPCHK(h, hipMemcpy(&err, h->d_err + 1, sizeof(int), hipMemcpyDeviceToHost));
-    if (!err) return MHNSW_OK;
-    HIPCHK(h, hipMemset(h->d_err + 1, 0, sizeof(int)));
-    if (err & 4) return fail(h, MHNSW_EINTERNAL, "out-of-range node id in adjacency (graph corrupt)");
-    if (err & 8) return fail(h, MHNSW_EINVAL, "unknown filter in filter_of");
-    return fail(h, MHNSW_EINTERNAL, "visited set overflow (raise vis_log2)");
+    if (err) HIPCHK(h, hipMemset(h->d_err + 1, 0, sizeof(int)));
+    return device_error(h, err);
 }
 
 // ---- filters (filtered search) ----

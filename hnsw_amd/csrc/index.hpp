@@ -280,8 +280,7 @@ int add_impl(mhnsw_index* h, const int64_t* keys, const float* vecs, bool vecs_o
 int beam_vis_entries(const mhnsw_index* h);
 int drain(mhnsw_index* h);
 int search_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int mode, int ef, const int64_t* entry_key, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool timing, int32_t* out_ids = nullptr, bool sticky = false);
-int order_meta(mhnsw_index* h, hipStream_t s);
-int search_body(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int mode, int ef, const int64_t* entry_key, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool timing, int32_t* out_ids, bool sticky);
+int device_error(mhnsw_index* h, int err);
 void reset_graph(mhnsw_index* h);
 constexpr int MHNSW_MAX_FILTERS = 1024;
 void drop_filters(mhnsw_index* h);

@@ -1,8 +1,11 @@
-// search_host.cpp -- host orchestration of the searches (graph.go:534-625,
-// 1047-1110, 1116-1537): argument checks with the reference's error texts,
-// stream ordering of the *_device calls, the beam / compat launches, and the
-// exact path (score GEMM, fused preselection, bucket select, canonical re-rank,
-// certificate, fallback); the negative-example re-ranking.
+// search_host.cpp -- host orchestration of the searches (graph.go:534-625, 1047-1110,
+// 1116-1537).  An entry point describes its call as a SearchCall and runs in on_scratch
+// (stream ordering of the *_device calls).  search_plain and search_filtered check the
+// arguments in their own order, with the reference's error texts, and share stage (queries,
+// outputs, error word), walk_args (the walk kernels' SearchArgs, the visited-set rule), finish
+// and read_error / device_error.  The plain search is exact_prepare + exact_run (score GEMM,
+// fused preselection, bucket select, canonical re-rank, certificate, fallback), beam_search
+// or compat_search.  Last, the negative-example re-ranking.
 #include "index.hpp"
 
 using namespace mhh;
@@ -25,9 +28,156 @@ int drain(mhnsw_index* h) {
     return 0;
 }
 
-int search_body(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int mode, int ef,
-                const int64_t* entry_key, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool timing,
-                int32_t* out_ids, bool sticky);
+// A search's device error word as the call's error.  (Only the filtered kernel sets bit 8:
+// the plain and negatives paths, which never tested it, report what they always did.)
+int device_error(mhnsw_index* h, int err) {
+    if (!err) return 0;
+    if (err & 4) return fail(h, MHNSW_EINTERNAL, "out-of-range node id in adjacency (graph corrupt)");
+    if (err & 8) return fail(h, MHNSW_EINVAL, "unknown filter in filter_of");
+    return fail(h, MHNSW_EINTERNAL, "visited set overflow (raise vis_log2)");
+}
+
+// One search as its entry point describes it; dk .. errw are what stage() adds: the
+// outputs on the device (the caller's, or scratch) and the kernels' error word.
+struct SearchCall {
+    const float* queries;  // [B * dim], on the host or (on_device) on the device, as the outputs
+    bool on_device;
+    int64_t B;
+    int dim, k;
+    int64_t* okeys;
+    float* odist;
+    int32_t* on;
+    int32_t* out_ids;  // [B * k] internal ids (device, nullable)
+    hipStream_t s;
+    bool sticky;  // report into d_err[1] (a *_device call, mhnsw_device_status), else into d_err[0], zeroed first
+    bool timing;  // ev0 / ev1 around the search kernels
+    int64_t* dk;
+    float* dd;
+    int32_t* dn;
+    int* errw;
+};
+
+// every search: after the scratch's previous user (another stream); the event is recorded on failure too
+template <class Body>
+static int on_scratch(mhnsw_index* h, hipStream_t s, Body body) {
+    if (h->scr_valid && h->scr_stream != s) HIPCHK(h, hipStreamWaitEvent(s, h->scr_ev, 0));
+    const int r = body();
+    HIPCHK(h, hipEventRecord(h->scr_ev, s));
+    h->scr_stream = s;
+    h->scr_valid = true;
+    return r;
+}
+
+// k, the dimension, the mode (a filtered search is a beam search) and the flat index, in this order
+static int check_args(mhnsw_index* h, const SearchCall& c, int mode) {
+    if (c.k <= 0) return fail(h, MHNSW_EK, "k must be greater than 0, got %d", c.k);  // graph.go:542-544
+    if (h->layers_exist && h->dim != c.dim) {                                          // graph.go:547-552
+        if (c.B == 1) return fail(h, MHNSW_EDIM, "embedding dimension mismatch: %d != %d", h->dim, c.dim);
+        return fail(h, MHNSW_EDIM, "embedding dimension mismatch for query %d: %d != %d", 0, h->dim, c.dim);
+    }
+    if (mode < 0 || mode > 2) return fail(h, MHNSW_EINVAL, "unknown search mode %d", mode);
+    if (h->build_mode == MHNSW_BUILD_FLAT && mode != MHNSW_MODE_EXACT)
+        return fail(h, MHNSW_EUNSUPPORTED, "flat index (build_mode 2) supports exact search only");
+    return 0;
+}
+
+// graph.go:554-556: an empty index (no layers, or no live row) answers nil, nil
+static int zero_counts(mhnsw_index* h, const SearchCall& c) {
+    if (c.on_device)
+        HIPCHK(h, hipMemsetAsync(c.on, 0, c.B * 4, c.s));
+    else
+        memset(c.on, 0, c.B * 4);
+    return 0;
+}
+
+// the queries padded into qpad, the device output buffers, the error word
+static int stage(mhnsw_index* h, SearchCall& c) {
+    int r;
+    if ((r = ensure_buf(h, h->qpad, (size_t)c.B * h->pitch))) return r;
+    if (!c.on_device) {
+        if ((r = ensure_buf(h, h->tmp, (size_t)c.B * c.dim))) return r;
+        HIPCHK(h, hipMemcpyAsync(h->tmp.p, c.queries, (size_t)c.B * c.dim * 4, hipMemcpyHostToDevice, c.s));
+    }
+    LCHK(h, launch_pad_rows(c.on_device ? c.queries : h->tmp.p, c.B, c.dim, h->qpad.p, h->pitch, c.s));
+    if (!c.on_device && ((r = ensure_buf(h, h->okeys, (size_t)c.B * c.k)) ||
+                         (r = ensure_buf(h, h->odist, (size_t)c.B * c.k)) || (r = ensure_buf(h, h->on, (size_t)c.B))))
+        return r;
+    c.dk = c.on_device ? c.okeys : h->okeys.p;
+    c.dd = c.on_device ? c.odist : h->odist.p;
+    c.dn = c.on_device ? c.on : h->on.p;
+    c.errw = c.sticky ? h->d_err + 1 : h->d_err;
+    if (!c.sticky) HIPCHK(h, hipMemsetAsync(h->d_err, 0, sizeof(int), c.s));
+    return 0;
+}
+
+// d_err[0] once the stream's work is done, as the call's error
+static int read_error(mhnsw_index* h, hipStream_t s) {
+    int err = 0;
+    HIPCHK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return device_error(h, err);
+}
+
+// a search whose kernels are enqueued: a host-pointer call waits for its results
+static int finish(mhnsw_index* h, const SearchCall& c) {
+    h->have_timing = c.timing;
+    h->stats_host[6] += c.B;
+    if (c.on_device) return 0;
+    HIPCHK(h, hipMemcpyAsync(c.okeys, c.dk, (size_t)c.B * c.k * 8, hipMemcpyDeviceToHost, c.s));
+    HIPCHK(h, hipMemcpyAsync(c.odist, c.dd, (size_t)c.B * c.k * 4, hipMemcpyDeviceToHost, c.s));
+    HIPCHK(h, hipMemcpyAsync(c.on, c.dn, (size_t)c.B * 4, hipMemcpyDeviceToHost, c.s));
+    return read_error(h, c.s);
+}
+
+// the search kernels run on the caller's stream; metadata goes up on the handle's
+static int order_meta(mhnsw_index* h, hipStream_t s) {
+    if (s == h->stream) return 0;
+    HIPCHK(h, hipEventRecord(h->meta_ev, h->stream));
+    HIPCHK(h, hipStreamWaitEvent(s, h->meta_ev, 0));
+    return 0;
+}
+
+// The walk kernels' arguments (beam, compat, filtered), the graph's metadata brought up to date.
+// ef: the walk's layer-0 list (the filtered search's route list); lds_tier: the launch keeps it in LDS.
+static int walk_args(mhnsw_index* h, const SearchCall& c, int top, uint32_t entry, int ef, bool lds_tier, SearchArgs& a) {
+    int r;
+    if ((r = sync_layer_entries(h)) || (r = sync_layer_table(h)) || (r = order_meta(h, c.s))) return r;
+    const int width = std::max(ef, c.k);
+    a.g = graph_view(h);
+    a.g.err = c.errw;
+    a.q = h->qpad.p;
+    a.B = c.B;
+    a.k = c.k;
+    a.ef = ef;
+    a.top = top;
+    a.entry = entry;
+    a.layer_entry = h->d_layer_entry;
+    a.out_keys = c.dk;
+    a.out_dist = c.dd;
+    a.out_n = c.dn;
+    a.out_ids = c.out_ids;
+    a.stats = h->d_stats;
+    a.err = c.errw;
+    a.vis_log2 = h->vis_log2;
+    a.vis_n = beam_vis_entries(h);
+    // the compact set holds 8,192 ids in 16 KiB (the 32-bit set 5,120 in 20 KiB):
+    // fewer resets at large ef, the same results either way.  Below ef 129 the
+    // 32-bit set rarely fills and its single-CAS probe is the cheaper one
+    // (the compact probe cost 1 % at the headline ef 64).
+    // (only where the compact set holds more ids than the 32-bit one in the LDS
+    // it is given: a user who raised vis_entries past 8,192 keeps that set)
+    a.vis16 = h->vis_compact && width > 128 && h->capn <= (int64_t(1) << 24) &&
+              (int64_t)a.vis_n >= (int64_t)VIS16_WORDS && a.vis_n < VIS16_HOMES;
+    // the LDS-list tier re-seeds up to `width` ids after a visited reset: an
+    // automatically sized 32-bit set holds at least 4 width entries there (at
+    // 5,120, resetting at 3/4 full, ef 2048 would reset every few steps).  An
+    // explicit vis_entries is kept as given: the results do not depend on it.  (2048: the tier's limit)
+    if (lds_tier && !a.vis16 && h->vis_entries <= 0) a.vis_n = std::max(a.vis_n, 4 * std::min(width, 2048));
+    a.upper_ef = h->upper_ef;
+    a.mw_max_b = h->beam_mw_max_b;
+    a.expand = h->search_expand;
+    return 0;
+}
 
 // The ordered beam search's sort key: the node the descent stood on when it left
 // layer key_top in the most significant field, then the nodes of the
@@ -40,7 +190,7 @@ int search_body(mhnsw_index* h, const float* queries, bool on_device, int64_t B,
 // whose only layer is 0 has no field: every key is 0.
 constexpr int ORDER_KEY_FIELDS = 3;
 constexpr int64_t ORDER_CELL_QUERIES = 128;
-void order_key_layers(const mhnsw_index* h, int64_t B, int top, SearchArgs& a) {
+static void order_key_layers(const mhnsw_index* h, int64_t B, int top, SearchArgs& a) {
     int bits = 1;
     while (bits < 31 && (int64_t(1) << bits) < h->capn) ++bits;
     int kt = h->search_order_top;
@@ -54,52 +204,359 @@ void order_key_layers(const mhnsw_index* h, int64_t B, int top, SearchArgs& a) {
     a.key_hash = a.key_id_bits < bits;
 }
 
-// every search: order after the previous scratch user (another stream), and
-// after the metadata copies this call makes on the handle's stream.  sticky:
-// the kernels report into d_err[1] (an asynchronous *_device search the caller
-// checks with mhnsw_device_status); otherwise into d_err[0], zeroed first.
-int search_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int mode, int ef,
-                const int64_t* entry_key, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool timing,
-                int32_t* out_ids, bool sticky) {
-    if (h->scr_valid && h->scr_stream != s) HIPCHK(h, hipStreamWaitEvent(s, h->scr_ev, 0));
-    const int r = search_body(h, queries, on_device, B, dim, k, mode, ef, entry_key, okeys, odist, on, s, timing,
-                              out_ids, sticky);
-    HIPCHK(h, hipEventRecord(h->scr_ev, s));
-    h->scr_stream = s;
-    h->scr_valid = true;
-    return r;
-}
-
-// the search kernels run on the caller's stream; metadata goes up on the handle's
-int order_meta(mhnsw_index* h, hipStream_t s) {
-    if (s == h->stream) return 0;
-    HIPCHK(h, hipEventRecord(h->meta_ev, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(s, h->meta_ev, 0));
+static int beam_search(mhnsw_index* h, const SearchCall& c, SearchArgs& a) {
+    int r;
+    const int64_t B = c.B;
+    hipStream_t s = c.s;
+    if (std::max(a.ef, a.k) > 2048) return fail(h, MHNSW_EUNSUPPORTED, "beam mode supports max(ef,k) <= 2048");
+    a.lds_min_ef = h->beam_lds_min_ef;
+    // ordered path: the descent as a pre-pass, the queries sorted by descent
+    // path, layer 0 searched in that order (the one-wave kernels only)
+    const bool ordered = h->search_order && B >= h->search_order_min_b && !beam_small_batch(a);
+    size_t tmp_bytes = 0;
+    if (ordered) {
+        LCHK(h, order_sort_temp_bytes(B, &tmp_bytes));
+        if ((r = ensure_buf(h, h->ordkey, (size_t)2 * B)) || (r = ensure_buf(h, h->ordval, (size_t)3 * B)) ||
+            (r = ensure_buf(h, h->ordtmp, std::max<size_t>(tmp_bytes, 1))))
+            return r;
+        a.okey = h->ordkey.p;
+        a.oidx = h->ordval.p;
+        a.ep0 = h->ordval.p + 2 * B;
+        order_key_layers(h, B, a.top, a);
+        a.order_chunk = h->search_order_map == 0 ? (B + 7) / 8 : 0;
+    }
+    if (c.timing) HIPCHK(h, hipEventRecord(h->ev0, s));
+    int lr = 0;
+    if (ordered && !(lr = launch_beam_descend(a, h->lpr, h->vpl, s))) {
+        LCHK(h, launch_order_sort(h->ordkey.p, h->ordkey.p + B, h->ordval.p, h->ordval.p + B, B,
+                                  a.key_n * a.key_id_bits, h->ordtmp.p, tmp_bytes, s));
+        a.order = h->ordval.p + B;
+    }
+    if (!lr) lr = launch_search_beam(a, h->lpr, h->vpl, s);
+    if (lr == -2)
+        return fail(h, MHNSW_EUNSUPPORTED, "beam search LDS budget exceeded (ef=%d, k=%d, vis_entries=%d)", a.ef, a.k,
+                    a.vis_n);
+    LCHK(h, lr);
+    if (c.timing) HIPCHK(h, hipEventRecord(h->ev1, s));
     return 0;
 }
 
-int search_body(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int mode, int ef,
-                const int64_t* entry_key, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool timing,
-                int32_t* out_ids, bool sticky) {
+static int compat_search(mhnsw_index* h, const SearchCall& c, const SearchArgs& a) {
+    if (c.timing) HIPCHK(h, hipEventRecord(h->ev0, c.s));
+    int lr = launch_search_compat(a, h->lpr, h->vpl, c.s);
+    if (lr == -2) return fail(h, MHNSW_EUNSUPPORTED, "compat search LDS budget exceeded (ef=%d, k=%d)", a.ef, a.k);
+    LCHK(h, lr);
+    if (c.timing) HIPCHK(h, hipEventRecord(h->ev1, c.s));
+    return 0;
+}
+
+// what exact_prepare decides for exact_run (the names are the two functions' locals)
+struct ExactPlan {
+    bool split, h1, h2;
+    int kk, nseg, ev, bm, stride, J, sseg, rcap, rsub, scap;
+    int64_t ldS, qc, seglen, nnt, nsamp, sseglen;
+    const uint8_t* xdead;
+    GraphDev g;
+    CertArgs cert;
+};
+
+// the exact path's workspace, the rows it skips and the certificate constants
+static int exact_prepare(mhnsw_index* h, const SearchCall& c, ExactPlan& plan) {
+    int r;
+    const int k = c.k;
+    hipStream_t s = c.s;
+    if (k > 256) return fail(h, MHNSW_EUNSUPPORTED, "exact mode supports k <= 256");
+    const bool split = h->exact_precision != 0;
+    // fp16 1-product with the fused preselection (needs one full sample tile of rows)
+    const bool h1 = h->exact_precision == 3 && h->n >= H1_BN;
+    const bool h2 = h->exact_precision >= 2;  // fp16 row plane (1- and 2-product)
+    // preselect width: the fp16 2-product scores carry a ~2x larger error bound, so the
+    // kk-th score must sit further from the k-th distance for the certificate
+    const int kk = h->exact_kk > 0 ? std::min(256, std::max(h->exact_kk, k))
+                                   : std::min(256, h2 ? std::max(2 * k, 64) : std::max(2 * k, k + 16));
+    const int64_t ldS = (h->n + 255) / 256 * 256;
+    const int64_t budget = (int64_t)4 << 30;  // score workspace bytes
+    int64_t qc = std::max<int64_t>(1, std::min<int64_t>(c.B, budget / (ldS * 4)));
+    qc = std::min<int64_t>(qc, 4096);
+    if ((r = ensure_buf(h, h->qnorm, (size_t)c.B)) ||
+        (r = ensure_buf(h, h->cand, (size_t)qc * kk)) || (r = ensure_buf(h, h->xbound, (size_t)qc)) ||
+        (r = ensure_buf(h, h->xflag, (size_t)qc)) || (r = ensure_buf(h, h->xflagged, (size_t)qc)) ||
+        (r = ensure_buf(h, h->xnflag, 1)) || (r = ensure_buf(h, h->xmaxn, 1)))
+        return r;
+    // selection: enough (query, row-segment) waves to stream the score rows at full rate
+    auto segs = [&](int64_t rows, int& ns, int64_t& sl) {
+        ns = (int)std::min<int64_t>(16, std::max<int64_t>(1, (16384 + qc - 1) / qc));
+        ns = (int)std::max<int64_t>(1, std::min<int64_t>(ns, (rows + 4095) / 4096));
+        ns = std::max(1, std::min(ns, 1024 / kk));  // merge holds nseg * kk entries
+        sl = ((rows + ns - 1) / ns + 1023) / 1024 * 1024;
+    };
+    int nseg;
+    int64_t seglen;
+    segs(h->n, nseg, seglen);
+    if ((r = ensure_buf(h, h->xsegd, (size_t)qc * nseg * kk)) || (r = ensure_buf(h, h->xsegi, (size_t)qc * nseg * kk)))
+        return r;
+    // fused preselection (h1): the sample = every stride-th full row tile (about 32
+    // tiles), its J-th best score per query is the threshold (J = kk when the
+    // sample is every tile); a row passes at a rate of ~J / sample rows
+    // the GEMM variant this search runs (exact_tile 0: the default, k_h1_pp16; a shape
+    // it does not admit runs the ring kernel's filter)
+    const int ev = h1_effective_variant(h->exact_tile, h->pitch, std::max<int64_t>(qc, h->capn));
+    const int bm = h1_tile_bm(ev);
+    const int64_t nnt = (h->n + H1_BN - 1) / H1_BN, nqt = (qc + bm - 1) / bm;
+    const int stride = (int)std::max<int64_t>(1, std::min<int64_t>(128, (nnt + h->exact_sample - 1) / h->exact_sample));
+    const int64_t nsamp = h1 ? ((h->n / H1_BN) - 1) / stride + 1 : 0;  // sampled full tiles
+    const int J = stride < 8 ? kk : h->exact_thr_rank > 0 ? std::min(kk, std::max(k, h->exact_thr_rank)) : std::max(k, kk / 8);
+    // the score workspace: every (query, row) score (precisions 0-2, and their
+    // fallback), or only the sample's (fused path: its fallback streams distances
+    // into per-segment lists, k_fallback_select)
+    if ((r = ensure_buf(h, h->scores, (size_t)qc * (h1 ? (size_t)std::max<int64_t>(nsamp, 1) * H1_BN : (size_t)ldS))))
+        return r;
+    int sseg = 1;
+    int64_t sseglen = 0;
+    if (h1) {
+        segs(nsamp * H1_BN, sseg, sseglen);
+        sseg = std::max(1, std::min(sseg, 1024 / J));
+    }
+    // pairs per tile region / per query sub-bucket: 4x what the threshold lets
+    // through on average (~J N / ns per query, ~bm J BN / ns per tile), with floors
+    const int64_t ns = std::max<int64_t>(1, nsamp * H1_BN);
+    // (a multiple of 8: k_h1_pp16 splits each tile's region among its 8 waves)
+    // record-mode variants: per wave 4x the expected records (<= one per passing pair,
+    // at most 8 block rows x 64 lanes), H1_REC uint2 each
+    const int rcap = h1_records(ev)
+                         ? 8 * H1_REC * (int)std::min<int64_t>(512, std::max<int64_t>(64, 4 * bm * J * H1_BN / ns / 8))
+                         : (int)std::min<int64_t>((int64_t)bm * H1_BN, std::max<int64_t>(2048, 4 * bm * J * H1_BN / ns) + 7) / 8 * 8;
+    const int rsub = h1_region_split(ev);
+    const int scap = (int)std::min<int64_t>(std::max<int64_t>(h->n, 1),
+                                            std::max<int64_t>(512, 8 * J * h->n / ns / H1_BSUB));
+    if (h1 && ((r = ensure_buf(h, h->h1thr, (size_t)qc)) || (r = ensure_buf(h, h->h1c, (size_t)nqt * bm + 256)) ||
+               (r = ensure_buf(h, h->h1s, (size_t)nqt * bm + 256)) ||
+               (r = ensure_buf(h, h->h1region, (size_t)nqt * nnt * rcap)) ||
+               (r = ensure_buf(h, h->h1rcnt, (size_t)nqt * nnt * rsub)) ||
+               (r = ensure_buf(h, h->h1xw, (size_t)std::max<int64_t>(h->n, 1) * 4)) ||
+               (r = ensure_buf(h, h->h1qcnt, (size_t)qc * H1_BSUB * H1_CSTRIDE)) || (r = ensure_buf(h, h->h1ovf, (size_t)qc)) ||
+               (r = ensure_buf(h, h->h1bucket, (size_t)qc * H1_BSUB * scap)) || (r = ensure_buf(h, h->qerr, 1)) ||
+               (r = ensure_buf(h, h->xsegd, (size_t)qc * sseg * J)) ||
+               (r = ensure_buf(h, h->xsegi, (size_t)qc * sseg * J))))
+        return r;
+    if (split) {
+        const int64_t plane = h->capn * h->pitch;
+        const int kind = h2 ? 2 : 1;
+        if (h->xsplit.n < (size_t)plane * 2 || h->xsplit_plane != plane || h->xsplit_kind != kind) {
+            if ((r = ensure_buf(h, h->xsplit, (size_t)plane * 2))) return r;
+            h->xsplit_rows = 0;
+            h->xsplit_plane = plane;
+            h->xsplit_kind = kind;
+        }
+        if ((r = ensure_buf(h, h->qsplit, (size_t)qc * h->pitch * 2))) return r;
+        if (h2 && ((r = ensure_buf(h, h->xinv, (size_t)h->capn)) || (r = ensure_buf(h, h->qinv, (size_t)qc)) ||
+                   (r = ensure_buf(h, h->xerr, 1))))
+            return r;
+    }
+    LCHK(h, launch_norms(h->qpad.p, 0, c.B, h->pitch, h->lpr, h->vpl, h->qnorm.p, s));
+    if ((r = sync_layer_table(h)) || (r = order_meta(h, s))) return r;
+    GraphDev g = graph_view(h);
+    g.err = c.errw;
+    // rows the brute force skips: deleted ones, and the live rows of a failed
+    // insert that never reached layer 0 (graph.go:1009 leaves them in upper
+    // layers only; Search cannot return them)
+    const uint8_t* xdead = h->any_dead ? h->dead : nullptr;
+    if (h->partial_rows && h->xgone_epoch != h->mut_epoch) {  // rebuilt only after a mutation
+        // a Delete or a replacement sweep may have killed the last partial rows
+        std::vector<uint8_t> gone((size_t)h->n);
+        int64_t partial = 0;
+        for (int64_t i = 0; i < h->n; ++i) {
+            const bool p = !h->hdead[i] && !in_layer(h, i, 0);
+            partial += p;
+            gone[i] = h->hdead[i] || p;
+        }
+        h->partial_rows = partial;
+        if (partial) {
+            if ((r = ensure_buf(h, h->xgone, (size_t)std::max<int64_t>(h->n, 1)))) return r;
+            HIPCHK(h, hipMemcpyAsync(h->xgone.p, gone.data(), (size_t)h->n, hipMemcpyHostToDevice, s));
+            HIPCHK(h, hipStreamSynchronize(s));
+        }
+        h->xgone_epoch = h->mut_epoch;
+    }
+    if (h->partial_rows) xdead = h->xgone.p;
+    g.dead = xdead;
+    // certificate constants (u = 2^-24; gamma_n = n u / (1 - n u) bounds any
+    // order of n-term f32 summation relative to the sum of magnitudes)
+    const double u = std::ldexp(1.0, -24);
+    auto gam = [&](double nn) { return nn * u / (1.0 - nn * u); };
+    // products per element: f32 1, bf16x3 3, fp16 2-product 2, fp16 1-product 1.  Split
+    // error: bf16x3 drops ql.xl and the planes' tails (3.02 * 2^-16); fp16 2-product
+    // rounds the rows to fp16 (2^-11 |x|, Cauchy-Schwarz) and the queries to hi + lo
+    // (2^-21); fp16 1-product rounds both once
+    const double g_mfma = gam((h1 ? 1.0 : h2 ? 2.0 : split ? 3.0 : 1.0) * h->pitch + 1);
+    // (fp16: the rows' part -- and the queries' in the 1-product -- is the measured
+    // max |x' - x| / |x| <= 2^-11, added on the device)
+    const double e_split = h1 ? 0.0 : h2 ? std::ldexp(1.0, -21) : split ? 3.02 * std::ldexp(1.0, -16) : 0.0;
+    const double g_can = gam(4.0 * h->vpl + 8);  // canonical: 4*VPL fmaf per lane + 6 butterfly levels
+    CertArgs cert{};
+    cert.qnorm = h->qnorm.p;
+    cert.xmax = h->xmaxn.p;
+    cert.eps_cos = (float)(1.01 * ((g_mfma + e_split + g_can) * (1.0 + 1e-4) + 16 * u));
+    cert.eps_dot = (float)(1.01 * (g_mfma + e_split + g_can));
+    cert.c_l2 = (float)(1.01 * (2.0 * gam(4.0 * h->vpl + 10) + 16 * u));
+    cert.flag = h->xflag.p;
+    cert.flagged = h->xflagged.p;
+    cert.nflag = h->xnflag.p;
+    cert.stats = h->d_stats + 3;
+    cert.xerr = h2 ? h->xerr.p : nullptr;
+    cert.qerr = h1 ? h->qerr.p : nullptr;
+    plan = ExactPlan{split, h1, h2, kk, nseg, ev, bm, stride, J, sseg, rcap, rsub, scap, ldS, qc, seglen, nnt, nsamp, sseglen,
+                     xdead, g, cert};
+    return 0;
+}
+
+// the exact path's kernels: per chunk of qc queries the scores, the selection, the re-rank and the fallback
+static int exact_run(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan) {
+    const auto& [split, h1, h2, kk, nseg, ev, bm, stride, J, sseg, rcap, rsub, scap, ldS, qc, seglen, nnt, nsamp, sseglen,
+                 xdead, g, cert] = plan;
+    const int k = c.k;
+    hipStream_t s = c.s;
+    if (c.timing) HIPCHK(h, hipEventRecord(h->ev0, s));
+    if (split && h->xsplit_rows < h->n) {
+        uint16_t* xh = h->xsplit.p;
+        uint16_t* xl = h->xsplit.p + (size_t)h->capn * h->pitch;
+        if (h2) {
+            if (h->xsplit_rows == 0) HIPCHK(h, hipMemsetAsync(h->xerr.p, 0, sizeof(float), s));
+            LCHK(h, launch_split_h16(h->vecs, h->xsplit_rows, h->n, h->pitch, h->capn, xh, nullptr, h->xinv.p,
+                                     h->xerr.p, s));
+        }
+        else
+            LCHK(h, launch_split_rows(h->vecs, h->xsplit_rows, h->n, h->pitch, h->capn, xh, xl, s));
+        h->xsplit_rows = h->n;
+    }
+    if (h->metric == EUCLIDEAN) {
+        HIPCHK(h, hipMemsetAsync(h->xmaxn.p, 0, sizeof(float), s));
+        LCHK(h, launch_max_norm(h->norms, h->n, h->xmaxn.p, s));
+    }
+    for (int64_t q0 = 0; q0 < c.B; q0 += qc) {
+        const int64_t nb = std::min(qc, c.B - q0);
+        ExactArgs a{};
+        a.X = h->vecs;
+        a.xnorm = h->norms;
+        a.dead = xdead;
+        a.N = h->n;
+        a.Q = h->qpad.p + (size_t)q0 * h->pitch;
+        a.qnorm = h->qnorm.p + q0;
+        a.B = nb;
+        a.pitch = h->pitch;
+        a.dim = h->dim;
+        a.metric = h->metric;
+        a.scores = h->scores.p;
+        a.ldS = ldS;
+        a.kk = kk;
+        a.cand = h->cand.p;
+        a.bound = h->xbound.p;
+        a.nseg = nseg;
+        a.seglen = seglen;
+        a.seg_d = h->xsegd.p;
+        a.seg_i = h->xsegi.p;
+        int64_t* ok_ = c.dk + q0 * k;
+        float* od_ = c.dd + q0 * k;
+        int32_t* on_ = c.dn + q0;
+        int32_t* oi_ = c.out_ids ? c.out_ids + q0 * k : nullptr;
+        if (split) {
+            a.Xh = h->xsplit.p;
+            a.Xl = h->xsplit.p + (size_t)h->capn * h->pitch;
+            a.ldXs = h->capn;
+            a.Qh = h->qsplit.p;
+            a.Ql = h->qsplit.p + (size_t)qc * h->pitch;
+            a.ldQs = qc;
+            if (h1) {
+                a.xinv = h->xinv.p;
+                a.qinv = h->qinv.p;
+                HIPCHK(h, hipMemsetAsync(h->qerr.p, 0, sizeof(float), s));
+                LCHK(h, launch_split_h16(a.Q, 0, nb, h->pitch, qc, h->qsplit.p, nullptr, h->qinv.p, h->qerr.p, s));
+                // 1. sample: every score of the sampled row tiles -> the kk-th best per query
+                ExactArgs as = a;
+                as.tile_stride = stride;
+                as.nsample_tiles = nsamp;
+                as.ldS = nsamp * H1_BN;
+                LCHK(h, launch_h1_sample(as, ev, s));
+                as.N = nsamp * H1_BN;
+                as.kk = J;
+                as.nseg = sseg;
+                as.seglen = sseglen;
+                as.bound = h->h1thr.p;
+                LCHK(h, launch_exact_select(as, s));
+                // 2. the full GEMM keeps the pairs that can beat it; 3. per-query buckets; 4. top-kk
+                LCHK(h, launch_ring_prep(h->h1thr.p, a.qnorm, a.qinv, nb, h->metric, h->h1c.p, h->h1s.p, s));
+                HIPCHK(h, hipMemsetAsync(h->h1qcnt.p, 0, (size_t)nb * H1_BSUB * H1_CSTRIDE * 4, s));
+                HIPCHK(h, hipMemsetAsync(h->h1ovf.p, 0, (size_t)nb, s));
+                a.tile_stride = 1;
+                a.ring_c = h->h1c.p;
+                a.ring_s = h->h1s.p;
+                a.region = h->h1region.p;
+                a.region_cnt = h->h1rcnt.p;
+                a.rcap = rcap;
+                a.xw = reinterpret_cast<const float4*>(h->h1xw.p);
+                if (q0 == 0)
+                    LCHK(h, launch_h1_rowconst(h->xinv.p, h->norms, xdead, h->n, h->metric,
+                                               reinterpret_cast<float4*>(h->h1xw.p), s));
+                if (c.timing && q0 == 0) HIPCHK(h, hipEventRecord(h->gev0, s));
+                LCHK(h, launch_h1_filter(a, ev, s));
+                if (c.timing && q0 == 0) {
+                    HIPCHK(h, hipEventRecord(h->gev1, s));
+                    h->have_gemm_timing = true;
+                }
+                const int64_t bqt = (nb + bm - 1) / bm;
+                LCHK(h, launch_bucket(h->h1region.p, h->h1rcnt.p, rcap, bqt * nnt, bqt, bm, H1_BN, nb, h->h1qcnt.p,
+                                      h->h1bucket.p, scap, h->h1ovf.p, rsub, h1_records(ev) ? 1 : 0, a, s));
+                LCHK(h, launch_select_bucket(a, h->h1qcnt.p, h->h1bucket.p, scap, h->h1ovf.p, h->h1thr.p, s));
+            } else if (h2) {
+                a.xinv = h->xinv.p;
+                a.qinv = h->qinv.p;
+                LCHK(h, launch_split_h16(a.Q, 0, nb, h->pitch, qc, h->qsplit.p, h->qsplit.p + (size_t)qc * h->pitch,
+                                         h->qinv.p, nullptr, s));
+                LCHK(h, launch_exact_scores_x2h(a, h->exact_tile, s));
+            } else {
+                LCHK(h, launch_split_rows(a.Q, 0, nb, h->pitch, qc, h->qsplit.p,
+                                          h->qsplit.p + (size_t)qc * h->pitch, s));
+                LCHK(h, launch_exact_scores_x3(a, h->exact_tile, s));
+            }
+        } else {
+            LCHK(h, launch_exact_scores(a, s));
+        }
+        if (!h1) LCHK(h, launch_exact_select(a, s));
+        if (h1 && h1_timing_diag(ev)) continue;  // timing diagnostic: no re-rank, no results
+        HIPCHK(h, hipMemsetAsync(h->xnflag.p, 0, sizeof(int32_t), s));
+        CertArgs c1 = cert;
+        c1.bound = h->xbound.p;
+        c1.qnorm = h->qnorm.p + q0;
+        LCHK(h, launch_rerank(a.Q, g, h->cand.p, kk, nb, h->lpr, h->vpl, k, ok_, od_, on_, oi_, c1, s));
+        // uncertified queries: canonical distances of every row, then select + re-rank again
+        ExactArgs a2 = a;
+        a2.only = h->xflag.p;
+        a2.bound = nullptr;
+        if (h1) {
+            LCHK(h, launch_fallback_select(a.Q, g, a2, h->lpr, h->vpl, s));
+        } else {
+            LCHK(h, launch_exact_fallback(a.Q, g, h->n, h->xflagged.p, h->xnflag.p, h->scores.p, ldS, h->lpr,
+                                          h->vpl, s));
+            LCHK(h, launch_exact_select(a2, s));
+        }
+        CertArgs c2{};
+        c2.only = h->xflag.p;
+        LCHK(h, launch_rerank(a.Q, g, h->cand.p, kk, nb, h->lpr, h->vpl, k, ok_, od_, on_, oi_, c2, s));
+    }
+    if (c.timing) HIPCHK(h, hipEventRecord(h->ev1, s));
+    if (h->exact_precision == 3 && h->n >= H1_BN && h1_timing_diag(ev))
+        return fail(h, MHNSW_EUNSUPPORTED, "exact_tile %d is a timing diagnostic: no results", h->exact_tile);
+    return 0;
+}
+
+// mhnsw_search*, and the candidate search of mhnsw_search_negatives
+static int search_plain(mhnsw_index* h, SearchCall& c, int mode, int ef, const int64_t* entry_key) {
     int r = validate(h);
     if (r) return r;
     h->have_gemm_timing = false;  // last_gemm_ns describes this search or none
-    if (k <= 0) return fail(h, MHNSW_EK, "k must be greater than 0, got %d", k);  // graph.go:542-544
-    if (h->layers_exist && h->dim != dim) {                                          // graph.go:547-552
-        if (B == 1) return fail(h, MHNSW_EDIM, "embedding dimension mismatch: %d != %d", h->dim, dim);
-        return fail(h, MHNSW_EDIM, "embedding dimension mismatch for query %d: %d != %d", 0, h->dim, dim);
-    }
-    if (mode < 0 || mode > 2) return fail(h, MHNSW_EINVAL, "unknown search mode %d", mode);
-    if (h->build_mode == MHNSW_BUILD_FLAT && mode != MHNSW_MODE_EXACT)
-        return fail(h, MHNSW_EUNSUPPORTED, "flat index (build_mode 2) supports exact search only");
-    if (B <= 0) return 0;
-    if (!h->layers_exist || live_count(h) == 0) {  // graph.go:554-556: nil, nil
-        if (on_device)
-            HIPCHK(h, hipMemsetAsync(on, 0, B * 4, s));
-        else
-            memset(on, 0, B * 4);
-        return 0;
-    }
+    if ((r = check_args(h, c, mode))) return r;
+    if (c.B <= 0) return 0;
+    if (!h->layers_exist || live_count(h) == 0) return zero_counts(h, c);
     if (ef <= 0) ef = h->ef;
     const int top = top_live_layer(h);
     uint32_t entry = (uint32_t)h->layers[top].entry;
@@ -108,523 +565,77 @@ int search_body(mhnsw_index* h, const float* queries, bool on_device, int64_t B,
         if (e < 0) return fail(h, MHNSW_EINVAL, "entry key %lld not in top layer", (long long)*entry_key);
         entry = (uint32_t)e;
     }
-    if ((r = ensure_buf(h, h->qpad, (size_t)B * h->pitch))) return r;
-    const float* qsrc = queries;
-    if (!on_device) {
-        if ((r = ensure_buf(h, h->tmp, (size_t)B * dim))) return r;
-        HIPCHK(h, hipMemcpyAsync(h->tmp.p, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, s));
-        qsrc = h->tmp.p;
-    }
-    LCHK(h, launch_pad_rows(qsrc, B, dim, h->qpad.p, h->pitch, s));
-    int64_t* dk = okeys;
-    float* dd = odist;
-    int32_t* dn = on;
-    if (!on_device) {
-        if ((r = ensure_buf(h, h->okeys, (size_t)B * k)) || (r = ensure_buf(h, h->odist, (size_t)B * k)) ||
-            (r = ensure_buf(h, h->on, (size_t)B)))
-            return r;
-        dk = h->okeys.p;
-        dd = h->odist.p;
-        dn = h->on.p;
-    }
-    int* errw = sticky ? h->d_err + 1 : h->d_err;
-    if (!sticky) HIPCHK(h, hipMemsetAsync(h->d_err, 0, sizeof(int), s));
+    if ((r = stage(h, c))) return r;
     if (mode == MHNSW_MODE_EXACT) {
-        if (k > 256) return fail(h, MHNSW_EUNSUPPORTED, "exact mode supports k <= 256");
-        const bool split = h->exact_precision != 0;
-        // fp16 1-product with the fused preselection (needs one full sample tile of rows)
-        const bool h1 = h->exact_precision == 3 && h->n >= H1_BN;
-        const bool h2 = h->exact_precision >= 2;  // fp16 row plane (1- and 2-product)
-        // preselect width: the fp16 2-product scores carry a ~2x larger error bound, so the
-        // kk-th score must sit further from the k-th distance for the certificate
-        const int kk = h->exact_kk > 0 ? std::min(256, std::max(h->exact_kk, k))
-                                       : std::min(256, h2 ? std::max(2 * k, 64) : std::max(2 * k, k + 16));
-        const int64_t ldS = (h->n + 255) / 256 * 256;
-        const int64_t budget = (int64_t)4 << 30;  // score workspace bytes
-        int64_t qc = std::max<int64_t>(1, std::min<int64_t>(B, budget / (ldS * 4)));
-        qc = std::min<int64_t>(qc, 4096);
-        if ((r = ensure_buf(h, h->qnorm, (size_t)B)) ||
-            (r = ensure_buf(h, h->cand, (size_t)qc * kk)) || (r = ensure_buf(h, h->xbound, (size_t)qc)) ||
-            (r = ensure_buf(h, h->xflag, (size_t)qc)) || (r = ensure_buf(h, h->xflagged, (size_t)qc)) ||
-            (r = ensure_buf(h, h->xnflag, 1)) || (r = ensure_buf(h, h->xmaxn, 1)))
-            return r;
-        // selection: enough (query, row-segment) waves to stream the score rows at full rate
-        auto segs = [&](int64_t rows, int& ns, int64_t& sl) {
-            ns = (int)std::min<int64_t>(16, std::max<int64_t>(1, (16384 + qc - 1) / qc));
-            ns = (int)std::max<int64_t>(1, std::min<int64_t>(ns, (rows + 4095) / 4096));
-            ns = std::max(1, std::min(ns, 1024 / kk));  // merge holds nseg * kk entries
-            sl = ((rows + ns - 1) / ns + 1023) / 1024 * 1024;
-        };
-        int nseg;
-        int64_t seglen;
-        segs(h->n, nseg, seglen);
-        if ((r = ensure_buf(h, h->xsegd, (size_t)qc * nseg * kk)) || (r = ensure_buf(h, h->xsegi, (size_t)qc * nseg * kk)))
-            return r;
-        // fused preselection (h1): the sample = every stride-th full row tile (about 32
-        // tiles), its J-th best score per query is the threshold (J = kk when the
-        // sample is every tile); a row passes at a rate of ~J / sample rows
-        // the GEMM variant this search runs (exact_tile 0: the default, k_h1_pp16; a shape
-        // it does not admit runs the ring kernel's filter)
-        const int ev = h1_effective_variant(h->exact_tile, h->pitch, std::max<int64_t>(qc, h->capn));
-        const int bm = h1_tile_bm(ev);
-        const int64_t nnt = (h->n + H1_BN - 1) / H1_BN, nqt = (qc + bm - 1) / bm;
-        const int stride = (int)std::max<int64_t>(1, std::min<int64_t>(128, (nnt + h->exact_sample - 1) / h->exact_sample));
-        const int64_t nsamp = h1 ? ((h->n / H1_BN) - 1) / stride + 1 : 0;  // sampled full tiles
-        const int J = stride < 8 ? kk : h->exact_thr_rank > 0 ? std::min(kk, std::max(k, h->exact_thr_rank)) : std::max(k, kk / 8);
-        // the score workspace: every (query, row) score (precisions 0-2, and their
-        // fallback), or only the sample's (fused path: its fallback streams distances
-        // into per-segment lists, k_fallback_select)
-        if ((r = ensure_buf(h, h->scores, (size_t)qc * (h1 ? (size_t)std::max<int64_t>(nsamp, 1) * H1_BN : (size_t)ldS))))
-            return r;
-        int sseg = 1;
-        int64_t sseglen = 0;
-        if (h1) {
-            segs(nsamp * H1_BN, sseg, sseglen);
-            sseg = std::max(1, std::min(sseg, 1024 / J));
-        }
-        // pairs per tile region / per query sub-bucket: 4x what the threshold lets
-        // through on average (~J N / ns per query, ~bm J BN / ns per tile), with floors
-        const int64_t ns = std::max<int64_t>(1, nsamp * H1_BN);
-        // (a multiple of 8: k_h1_pp16 splits each tile's region among its 8 waves)
-        // record-mode variants: per wave 4x the expected records (<= one per passing pair,
-        // at most 8 block rows x 64 lanes), H1_REC uint2 each
-        const int rcap = h1_records(ev)
-                             ? 8 * H1_REC * (int)std::min<int64_t>(512, std::max<int64_t>(64, 4 * bm * J * H1_BN / ns / 8))
-                             : (int)std::min<int64_t>((int64_t)bm * H1_BN, std::max<int64_t>(2048, 4 * bm * J * H1_BN / ns) + 7) / 8 * 8;
-        const int rsub = h1_region_split(ev);
-        const int scap = (int)std::min<int64_t>(std::max<int64_t>(h->n, 1),
-                                                std::max<int64_t>(512, 8 * J * h->n / ns / H1_BSUB));
-        if (h1 && ((r = ensure_buf(h, h->h1thr, (size_t)qc)) || (r = ensure_buf(h, h->h1c, (size_t)nqt * bm + 256)) ||
-                   (r = ensure_buf(h, h->h1s, (size_t)nqt * bm + 256)) ||
-                   (r = ensure_buf(h, h->h1region, (size_t)nqt * nnt * rcap)) ||
-                   (r = ensure_buf(h, h->h1rcnt, (size_t)nqt * nnt * rsub)) ||
-                   (r = ensure_buf(h, h->h1xw, (size_t)std::max<int64_t>(h->n, 1) * 4)) ||
-                   (r = ensure_buf(h, h->h1qcnt, (size_t)qc * H1_BSUB * H1_CSTRIDE)) || (r = ensure_buf(h, h->h1ovf, (size_t)qc)) ||
-                   (r = ensure_buf(h, h->h1bucket, (size_t)qc * H1_BSUB * scap)) || (r = ensure_buf(h, h->qerr, 1)) ||
-                   (r = ensure_buf(h, h->xsegd, (size_t)qc * sseg * J)) ||
-                   (r = ensure_buf(h, h->xsegi, (size_t)qc * sseg * J))))
-            return r;
-        if (split) {
-            const int64_t plane = h->capn * h->pitch;
-            const int kind = h2 ? 2 : 1;
-            if (h->xsplit.n < (size_t)plane * 2 || h->xsplit_plane != plane || h->xsplit_kind != kind) {
-                if ((r = ensure_buf(h, h->xsplit, (size_t)plane * 2))) return r;
-                h->xsplit_rows = 0;
-                h->xsplit_plane = plane;
-                h->xsplit_kind = kind;
-            }
-            if ((r = ensure_buf(h, h->qsplit, (size_t)qc * h->pitch * 2))) return r;
-            if (h2 && ((r = ensure_buf(h, h->xinv, (size_t)h->capn)) || (r = ensure_buf(h, h->qinv, (size_t)qc)) ||
-                       (r = ensure_buf(h, h->xerr, 1))))
-                return r;
-        }
-        LCHK(h, launch_norms(h->qpad.p, 0, B, h->pitch, h->lpr, h->vpl, h->qnorm.p, s));
-        if ((r = sync_layer_table(h)) || (r = order_meta(h, s))) return r;
-        GraphDev g = graph_view(h);
-        g.err = errw;
-        // rows the brute force skips: deleted ones, and the live rows of a failed
-        // insert that never reached layer 0 (graph.go:1009 leaves them in upper
-        // layers only; Search cannot return them)
-        const uint8_t* xdead = h->any_dead ? h->dead : nullptr;
-        if (h->partial_rows && h->xgone_epoch != h->mut_epoch) {  // rebuilt only after a mutation
-            // a Delete or a replacement sweep may have killed the last partial rows
-            std::vector<uint8_t> gone((size_t)h->n);
-            int64_t partial = 0;
-            for (int64_t i = 0; i < h->n; ++i) {
-                const bool p = !h->hdead[i] && !in_layer(h, i, 0);
-                partial += p;
-                gone[i] = h->hdead[i] || p;
-            }
-            h->partial_rows = partial;
-            if (partial) {
-                if ((r = ensure_buf(h, h->xgone, (size_t)std::max<int64_t>(h->n, 1)))) return r;
-                HIPCHK(h, hipMemcpyAsync(h->xgone.p, gone.data(), (size_t)h->n, hipMemcpyHostToDevice, s));
-                HIPCHK(h, hipStreamSynchronize(s));
-            }
-            h->xgone_epoch = h->mut_epoch;
-        }
-        if (h->partial_rows) xdead = h->xgone.p;
-        g.dead = xdead;
-        // certificate constants (u = 2^-24; gamma_n = n u / (1 - n u) bounds any
-        // order of n-term f32 summation relative to the sum of magnitudes)
-        const double u = std::ldexp(1.0, -24);
-        auto gam = [&](double nn) { return nn * u / (1.0 - nn * u); };
-        // products per element: f32 1, bf16x3 3, fp16 2-product 2, fp16 1-product 1.  Split
-        // error: bf16x3 drops ql.xl and the planes' tails (3.02 * 2^-16); fp16 2-product
-        // rounds the rows to fp16 (2^-11 |x|, Cauchy-Schwarz) and the queries to hi + lo
-        // (2^-21); fp16 1-product rounds both once
-        const double g_mfma = gam((h1 ? 1.0 : h2 ? 2.0 : split ? 3.0 : 1.0) * h->pitch + 1);
-        // (fp16: the rows' part -- and the queries' in the 1-product -- is the measured
-        // max |x' - x| / |x| <= 2^-11, added on the device)
-        const double e_split = h1 ? 0.0 : h2 ? std::ldexp(1.0, -21) : split ? 3.02 * std::ldexp(1.0, -16) : 0.0;
-        const double g_can = gam(4.0 * h->vpl + 8);  // canonical: 4*VPL fmaf per lane + 6 butterfly levels
-        CertArgs cert{};
-        cert.qnorm = h->qnorm.p;
-        cert.xmax = h->xmaxn.p;
-        cert.eps_cos = (float)(1.01 * ((g_mfma + e_split + g_can) * (1.0 + 1e-4) + 16 * u));
-        cert.eps_dot = (float)(1.01 * (g_mfma + e_split + g_can));
-        cert.c_l2 = (float)(1.01 * (2.0 * gam(4.0 * h->vpl + 10) + 16 * u));
-        cert.flag = h->xflag.p;
-        cert.flagged = h->xflagged.p;
-        cert.nflag = h->xnflag.p;
-        cert.stats = h->d_stats + 3;
-        cert.xerr = h2 ? h->xerr.p : nullptr;
-        cert.qerr = h1 ? h->qerr.p : nullptr;
-        if (timing) HIPCHK(h, hipEventRecord(h->ev0, s));
-        if (split && h->xsplit_rows < h->n) {
-            uint16_t* xh = h->xsplit.p;
-            uint16_t* xl = h->xsplit.p + (size_t)h->capn * h->pitch;
-            if (h2) {
-                if (h->xsplit_rows == 0) HIPCHK(h, hipMemsetAsync(h->xerr.p, 0, sizeof(float), s));
-                LCHK(h, launch_split_h16(h->vecs, h->xsplit_rows, h->n, h->pitch, h->capn, xh, nullptr, h->xinv.p,
-                                         h->xerr.p, s));
-            }
-            else
-                LCHK(h, launch_split_rows(h->vecs, h->xsplit_rows, h->n, h->pitch, h->capn, xh, xl, s));
-            h->xsplit_rows = h->n;
-        }
-        if (h->metric == EUCLIDEAN) {
-            HIPCHK(h, hipMemsetAsync(h->xmaxn.p, 0, sizeof(float), s));
-            LCHK(h, launch_max_norm(h->norms, h->n, h->xmaxn.p, s));
-        }
-        for (int64_t q0 = 0; q0 < B; q0 += qc) {
-            const int64_t nb = std::min(qc, B - q0);
-            ExactArgs a{};
-            a.X = h->vecs;
-            a.xnorm = h->norms;
-            a.dead = xdead;
-            a.N = h->n;
-            a.Q = h->qpad.p + (size_t)q0 * h->pitch;
-            a.qnorm = h->qnorm.p + q0;
-            a.B = nb;
-            a.pitch = h->pitch;
-            a.dim = h->dim;
-            a.metric = h->metric;
-            a.scores = h->scores.p;
-            a.ldS = ldS;
-            a.kk = kk;
-            a.cand = h->cand.p;
-            a.bound = h->xbound.p;
-            a.nseg = nseg;
-            a.seglen = seglen;
-            a.seg_d = h->xsegd.p;
-            a.seg_i = h->xsegi.p;
-            int64_t* ok_ = dk + q0 * k;
-            float* od_ = dd + q0 * k;
-            int32_t* on_ = dn + q0;
-            int32_t* oi_ = out_ids ? out_ids + q0 * k : nullptr;
-            if (split) {
-                a.Xh = h->xsplit.p;
-                a.Xl = h->xsplit.p + (size_t)h->capn * h->pitch;
-                a.ldXs = h->capn;
-                a.Qh = h->qsplit.p;
-                a.Ql = h->qsplit.p + (size_t)qc * h->pitch;
-                a.ldQs = qc;
-                if (h1) {
-                    a.xinv = h->xinv.p;
-                    a.qinv = h->qinv.p;
-                    HIPCHK(h, hipMemsetAsync(h->qerr.p, 0, sizeof(float), s));
-                    LCHK(h, launch_split_h16(a.Q, 0, nb, h->pitch, qc, h->qsplit.p, nullptr, h->qinv.p, h->qerr.p, s));
-                    // 1. sample: every score of the sampled row tiles -> the kk-th best per query
-                    ExactArgs as = a;
-                    as.tile_stride = stride;
-                    as.nsample_tiles = nsamp;
-                    as.ldS = nsamp * H1_BN;
-                    LCHK(h, launch_h1_sample(as, ev, s));
-                    as.N = nsamp * H1_BN;
-                    as.kk = J;
-                    as.nseg = sseg;
-                    as.seglen = sseglen;
-                    as.bound = h->h1thr.p;
-                    LCHK(h, launch_exact_select(as, s));
-                    // 2. the full GEMM keeps the pairs that can beat it; 3. per-query buckets; 4. top-kk
-                    LCHK(h, launch_ring_prep(h->h1thr.p, a.qnorm, a.qinv, nb, h->metric, h->h1c.p, h->h1s.p, s));
-                    HIPCHK(h, hipMemsetAsync(h->h1qcnt.p, 0, (size_t)nb * H1_BSUB * H1_CSTRIDE * 4, s));
-                    HIPCHK(h, hipMemsetAsync(h->h1ovf.p, 0, (size_t)nb, s));
-                    a.tile_stride = 1;
-                    a.ring_c = h->h1c.p;
-                    a.ring_s = h->h1s.p;
-                    a.region = h->h1region.p;
-                    a.region_cnt = h->h1rcnt.p;
-                    a.rcap = rcap;
-                    a.xw = reinterpret_cast<const float4*>(h->h1xw.p);
-                    if (q0 == 0)
-                        LCHK(h, launch_h1_rowconst(h->xinv.p, h->norms, xdead, h->n, h->metric,
-                                                   reinterpret_cast<float4*>(h->h1xw.p), s));
-                    if (timing && q0 == 0) HIPCHK(h, hipEventRecord(h->gev0, s));
-                    LCHK(h, launch_h1_filter(a, ev, s));
-                    if (timing && q0 == 0) {
-                        HIPCHK(h, hipEventRecord(h->gev1, s));
-                        h->have_gemm_timing = true;
-                    }
-                    const int64_t bqt = (nb + bm - 1) / bm;
-                    LCHK(h, launch_bucket(h->h1region.p, h->h1rcnt.p, rcap, bqt * nnt, bqt, bm, H1_BN, nb, h->h1qcnt.p,
-                                          h->h1bucket.p, scap, h->h1ovf.p, rsub, h1_records(ev) ? 1 : 0, a, s));
-                    LCHK(h, launch_select_bucket(a, h->h1qcnt.p, h->h1bucket.p, scap, h->h1ovf.p, h->h1thr.p, s));
-                } else if (h2) {
-                    a.xinv = h->xinv.p;
-                    a.qinv = h->qinv.p;
-                    LCHK(h, launch_split_h16(a.Q, 0, nb, h->pitch, qc, h->qsplit.p, h->qsplit.p + (size_t)qc * h->pitch,
-                                             h->qinv.p, nullptr, s));
-                    LCHK(h, launch_exact_scores_x2h(a, h->exact_tile, s));
-                } else {
-                    LCHK(h, launch_split_rows(a.Q, 0, nb, h->pitch, qc, h->qsplit.p,
-                                              h->qsplit.p + (size_t)qc * h->pitch, s));
-                    LCHK(h, launch_exact_scores_x3(a, h->exact_tile, s));
-                }
-            } else {
-                LCHK(h, launch_exact_scores(a, s));
-            }
-            if (!h1) LCHK(h, launch_exact_select(a, s));
-            if (h1 && h1_timing_diag(ev)) continue;  // timing diagnostic: no re-rank, no results
-            HIPCHK(h, hipMemsetAsync(h->xnflag.p, 0, sizeof(int32_t), s));
-            CertArgs c1 = cert;
-            c1.bound = h->xbound.p;
-            c1.qnorm = h->qnorm.p + q0;
-            LCHK(h, launch_rerank(a.Q, g, h->cand.p, kk, nb, h->lpr, h->vpl, k, ok_, od_, on_, oi_, c1, s));
-            // uncertified queries: canonical distances of every row, then select + re-rank again
-            ExactArgs a2 = a;
-            a2.only = h->xflag.p;
-            a2.bound = nullptr;
-            if (h1) {
-                LCHK(h, launch_fallback_select(a.Q, g, a2, h->lpr, h->vpl, s));
-            } else {
-                LCHK(h, launch_exact_fallback(a.Q, g, h->n, h->xflagged.p, h->xnflag.p, h->scores.p, ldS, h->lpr,
-                                              h->vpl, s));
-                LCHK(h, launch_exact_select(a2, s));
-            }
-            CertArgs c2{};
-            c2.only = h->xflag.p;
-            LCHK(h, launch_rerank(a.Q, g, h->cand.p, kk, nb, h->lpr, h->vpl, k, ok_, od_, on_, oi_, c2, s));
-        }
-        if (timing) HIPCHK(h, hipEventRecord(h->ev1, s));
-        if (h->exact_precision == 3 && h->n >= H1_BN && h1_timing_diag(ev))
-            return fail(h, MHNSW_EUNSUPPORTED, "exact_tile %d is a timing diagnostic: no results", h->exact_tile);
+        ExactPlan plan;
+        if (!(r = exact_prepare(h, c, plan))) r = exact_run(h, c, plan);
     } else {
-        if ((r = sync_layer_entries(h))) return r;
-        if ((r = sync_layer_table(h)) || (r = order_meta(h, s))) return r;
+        const bool beam = mode == MHNSW_MODE_BEAM;
         SearchArgs a;
-        a.g = graph_view(h);
-        a.g.err = errw;
-        a.q = h->qpad.p;
-        a.B = B;
-        a.k = k;
-        a.ef = ef;
-        a.top = top;
-        a.entry = entry;
-        a.layer_entry = h->d_layer_entry;
-        a.out_keys = dk;
-        a.out_dist = dd;
-        a.out_n = dn;
-        a.out_ids = out_ids;
-        a.stats = h->d_stats;
-        a.err = errw;
-        a.vis_log2 = h->vis_log2;
-        a.vis_n = beam_vis_entries(h);
-        // the compact set holds 8,192 ids in 16 KiB (the 32-bit set 5,120 in 20 KiB):
-        // fewer resets at large ef, the same results either way.  Below ef 129 the
-        // 32-bit set rarely fills and its single-CAS probe is the cheaper one
-        // (the compact probe cost 1 % at the headline ef 64).
-        // (only where the compact set holds more ids than the 32-bit one in the LDS
-        // it is given: a user who raised vis_entries past 8,192 keeps that set)
-        a.vis16 = h->vis_compact && std::max(ef, k) > 128 && h->capn <= (int64_t(1) << 24) &&
-                  (int64_t)a.vis_n >= (int64_t)VIS16_WORDS && a.vis_n < VIS16_HOMES;
-        a.upper_ef = h->upper_ef;
-        a.mw_max_b = h->beam_mw_max_b;
-        a.expand = h->search_expand;
-        if (mode == MHNSW_MODE_BEAM) {
-            const int efl = std::max(ef, k);
-            if (efl > 2048) return fail(h, MHNSW_EUNSUPPORTED, "beam mode supports max(ef,k) <= 2048");
-            a.lds_min_ef = h->beam_lds_min_ef;
-            // the LDS-list tier re-seeds up to efl ids after a visited reset: an
-            // automatically sized 32-bit set holds at least 4 efl entries there (at
-            // 5,120, resetting at 3/4 full, ef 2048 would reset every few steps).  An
-            // explicit vis_entries is kept as given: the results do not depend on it.
-            if (efl >= a.lds_min_ef && !a.vis16 && h->vis_entries <= 0) a.vis_n = std::max(a.vis_n, 4 * efl);
-            // ordered path: the descent as a pre-pass, the queries sorted by descent
-            // path, layer 0 searched in that order (the one-wave kernels only)
-            const bool ordered = h->search_order && B >= h->search_order_min_b && !beam_small_batch(a);
-            size_t tmp_bytes = 0;
-            if (ordered) {
-                LCHK(h, order_sort_temp_bytes(B, &tmp_bytes));
-                if ((r = ensure_buf(h, h->ordkey, (size_t)2 * B)) || (r = ensure_buf(h, h->ordval, (size_t)3 * B)) ||
-                    (r = ensure_buf(h, h->ordtmp, std::max<size_t>(tmp_bytes, 1))))
-                    return r;
-                a.okey = h->ordkey.p;
-                a.oidx = h->ordval.p;
-                a.ep0 = h->ordval.p + 2 * B;
-                order_key_layers(h, B, top, a);
-                a.order_chunk = h->search_order_map == 0 ? (B + 7) / 8 : 0;
-            }
-            if (timing) HIPCHK(h, hipEventRecord(h->ev0, s));
-            int lr = 0;
-            if (ordered && !(lr = launch_beam_descend(a, h->lpr, h->vpl, s))) {
-                LCHK(h, launch_order_sort(h->ordkey.p, h->ordkey.p + B, h->ordval.p, h->ordval.p + B, B,
-                                          a.key_n * a.key_id_bits, h->ordtmp.p, tmp_bytes, s));
-                a.order = h->ordval.p + B;
-            }
-            if (!lr) lr = launch_search_beam(a, h->lpr, h->vpl, s);
-            if (lr == -2)
-                return fail(h, MHNSW_EUNSUPPORTED, "beam search LDS budget exceeded (ef=%d, k=%d, vis_entries=%d)", ef, k,
-                            a.vis_n);
-            LCHK(h, lr);
-            if (timing) HIPCHK(h, hipEventRecord(h->ev1, s));
-        } else {
-            if (timing) HIPCHK(h, hipEventRecord(h->ev0, s));
-            int lr = launch_search_compat(a, h->lpr, h->vpl, s);
-            if (lr == -2) return fail(h, MHNSW_EUNSUPPORTED, "compat search LDS budget exceeded (ef=%d, k=%d)", ef, k);
-            LCHK(h, lr);
-            if (timing) HIPCHK(h, hipEventRecord(h->ev1, s));
-        }
+        if ((r = walk_args(h, c, top, entry, ef, beam && std::max(ef, c.k) >= h->beam_lds_min_ef, a))) return r;
+        r = beam ? beam_search(h, c, a) : compat_search(h, c, a);
     }
-    h->have_timing = timing;
-    h->stats_host[6] += B;
-    if (!on_device) {
-        HIPCHK(h, hipMemcpyAsync(okeys, dk, (size_t)B * k * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(odist, dd, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(on, dn, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-        int err = 0;
-        HIPCHK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (err & 4) return fail(h, MHNSW_EINTERNAL, "out-of-range node id in adjacency (graph corrupt)");
-        if (err) return fail(h, MHNSW_EINTERNAL, "visited set overflow (raise vis_log2)");
-    }
-    return 0;
+    return r ? r : finish(h, c);
 }
 
-// The filtered beam search (beam.hpp k_search_beam_filt): the fused launch over
-// the LDS list of `route` entries, results from the list of max(ef, k) allowed
-// rows.  Stream ordering, scratch and the error words as search_impl's.
-static int search_filtered_body(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int ef,
-                                int route, const int32_t* filter_of, int64_t* okeys, float* odist, int32_t* on,
-                                hipStream_t s, bool sticky) {
+// The filtered beam search (beam.hpp k_search_beam_filt): the fused launch over the LDS list of `route`
+// entries, results from the list of max(ef, k) allowed rows.  Always timed (c.timing is set).
+static int search_filtered(mhnsw_index* h, SearchCall& c, int ef, int route, const int32_t* filter_of) {
     int r = validate(h);
-    if (r) return r;
-    if (k <= 0) return fail(h, MHNSW_EK, "k must be greater than 0, got %d", k);
-    if (h->layers_exist && h->dim != dim) {
-        if (B == 1) return fail(h, MHNSW_EDIM, "embedding dimension mismatch: %d != %d", h->dim, dim);
-        return fail(h, MHNSW_EDIM, "embedding dimension mismatch for query %d: %d != %d", 0, h->dim, dim);
-    }
-    if (h->build_mode == MHNSW_BUILD_FLAT)
-        return fail(h, MHNSW_EUNSUPPORTED, "flat index (build_mode 2) supports exact search only");
+    if (r || (r = check_args(h, c, MHNSW_MODE_BEAM))) return r;
     if (ef <= 0) ef = h->ef;
-    const int E = std::max(ef, k);
+    const int E = std::max(ef, c.k);
     if (E > 128) return fail(h, MHNSW_EUNSUPPORTED, "filtered search supports max(ef,k) <= 128");
     if (route <= 0) route = h->filter_route;
     const int W = std::max(route, E);
     if (W > 2048) return fail(h, MHNSW_EUNSUPPORTED, "filtered search supports route <= 2048");  // (LL_MAX_EF)
-    if (B <= 0) return 0;
+    if (c.B <= 0) return 0;
     if (!filter_of) return fail(h, MHNSW_EINVAL, "filter_of must be non-NULL");
-    if (!on_device)
-        for (int64_t b = 0; b < B; ++b) {
+    if (!c.on_device)
+        for (int64_t b = 0; b < c.B; ++b) {
             const int32_t f = filter_of[b];
             if (f < -1 || (f >= 0 && (f >= (int)h->filters.size() || !h->filters[f].used)))
                 return fail(h, MHNSW_EINVAL, "unknown filter %d", f);
         }
-    if (!h->layers_exist || live_count(h) == 0) {
-        if (on_device)
-            HIPCHK(h, hipMemsetAsync(on, 0, B * 4, s));
-        else
-            memset(on, 0, B * 4);
-        return 0;
-    }
+    if (!h->layers_exist || live_count(h) == 0) return zero_counts(h, c);
     // a bitmap that has to grow with the rows moves: nothing enqueued may read it
     const size_t words = (size_t)((h->capn + 31) / 32);
-    for (const auto& F : h->filters)
-        if (F.used && F.bits.size() < words) {
-            if ((r = drain(h))) return r;
-            break;
-        }
+    const auto grows = [&](const mhnsw_index::Filter& F) { return F.used && F.bits.size() < words; };
+    if (std::any_of(h->filters.begin(), h->filters.end(), grows) && (r = drain(h))) return r;
     if ((r = filters_fit(h))) return r;
     const int top = top_live_layer(h);
-    if ((r = ensure_buf(h, h->qpad, (size_t)B * h->pitch))) return r;
-    const float* qsrc = queries;
-    const int32_t* dfof = filter_of;
-    if (!on_device) {
-        if ((r = ensure_buf(h, h->tmp, (size_t)B * dim)) || (r = ensure_buf(h, h->fof, (size_t)B))) return r;
-        HIPCHK(h, hipMemcpyAsync(h->tmp.p, queries, (size_t)B * dim * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(h->fof.p, filter_of, (size_t)B * 4, hipMemcpyHostToDevice, s));
-        qsrc = h->tmp.p;
-        dfof = h->fof.p;
+    if (!c.on_device) {  // (the filtered call's own upload, next to stage()'s of the queries)
+        if ((r = ensure_buf(h, h->fof, (size_t)c.B))) return r;
+        HIPCHK(h, hipMemcpyAsync(h->fof.p, filter_of, (size_t)c.B * 4, hipMemcpyHostToDevice, c.s));
     }
-    LCHK(h, launch_pad_rows(qsrc, B, dim, h->qpad.p, h->pitch, s));
-    int64_t* dk = okeys;
-    float* dd = odist;
-    int32_t* dn = on;
-    if (!on_device) {
-        if ((r = ensure_buf(h, h->okeys, (size_t)B * k)) || (r = ensure_buf(h, h->odist, (size_t)B * k)) ||
-            (r = ensure_buf(h, h->on, (size_t)B)))
-            return r;
-        dk = h->okeys.p;
-        dd = h->odist.p;
-        dn = h->on.p;
-    }
-    int* errw = sticky ? h->d_err + 1 : h->d_err;
-    if (!sticky) HIPCHK(h, hipMemsetAsync(h->d_err, 0, sizeof(int), s));
-    if ((r = sync_layer_entries(h))) return r;
-    if ((r = sync_layer_table(h)) || (r = order_meta(h, s))) return r;
-    SearchArgs a;
-    a.g = graph_view(h);
-    a.g.err = errw;
-    a.q = h->qpad.p;
-    a.B = B;
-    a.k = k;
-    a.ef = W;  // (the route list's width: FilterArgs::ef is the result list's)
-    a.top = top;
-    a.entry = (uint32_t)h->layers[top].entry;
-    a.layer_entry = h->d_layer_entry;
-    a.out_keys = dk;
-    a.out_dist = dd;
-    a.out_n = dn;
-    a.out_ids = nullptr;
-    a.stats = h->d_stats;
-    a.err = errw;
-    a.vis_log2 = h->vis_log2;
-    a.vis_n = beam_vis_entries(h);
-    // the visited set as the LDS-list tier's at max(ef, k) = W (search_body)
-    a.vis16 = h->vis_compact && W > 128 && h->capn <= (int64_t(1) << 24) && (int64_t)a.vis_n >= (int64_t)VIS16_WORDS &&
-              a.vis_n < VIS16_HOMES;
-    if (!a.vis16 && h->vis_entries <= 0) a.vis_n = std::max(a.vis_n, 4 * W);
-    a.upper_ef = h->upper_ef;
+    const FilterArgs f{h->d_filters, MHNSW_MAX_FILTERS, E, c.on_device ? filter_of : h->fof.p};
+    if ((r = stage(h, c))) return r;
+    SearchArgs a;  // (ef: the route list's width W, in LDS; FilterArgs::ef is the result list's)
+    if ((r = walk_args(h, c, top, (uint32_t)h->layers[top].entry, W, true, a))) return r;
     a.mw_max_b = 0;
     a.expand = 1;
-    FilterArgs f;
-    f.filters = h->d_filters;
-    f.nslots = MHNSW_MAX_FILTERS;
-    f.ef = E;
-    f.filter_of = dfof;
-    HIPCHK(h, hipEventRecord(h->ev0, s));
-    const int lr = launch_search_beam_filtered(a, f, h->lpr, h->vpl, s);
+    HIPCHK(h, hipEventRecord(h->ev0, c.s));
+    const int lr = launch_search_beam_filtered(a, f, h->lpr, h->vpl, c.s);
     if (lr == -2)
         return fail(h, MHNSW_EUNSUPPORTED, "filtered search LDS budget exceeded (route=%d, vis_entries=%d)", W, a.vis_n);
     LCHK(h, lr);
-    HIPCHK(h, hipEventRecord(h->ev1, s));
-    h->have_timing = true;
+    HIPCHK(h, hipEventRecord(h->ev1, c.s));
     h->have_gemm_timing = false;
-    h->stats_host[6] += B;
-    if (!on_device) {
-        HIPCHK(h, hipMemcpyAsync(okeys, dk, (size_t)B * k * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(odist, dd, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(on, dn, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-        int err = 0;
-        HIPCHK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (err & 4) return fail(h, MHNSW_EINTERNAL, "out-of-range node id in adjacency (graph corrupt)");
-        if (err & 8) return fail(h, MHNSW_EINVAL, "unknown filter in filter_of");
-        if (err) return fail(h, MHNSW_EINTERNAL, "visited set overflow (raise vis_log2)");
-    }
-    return 0;
+    return finish(h, c);
+}
+
+int search_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int mode, int ef,
+                const int64_t* entry_key, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool timing,
+                int32_t* out_ids, bool sticky) {
+    SearchCall c{queries, on_device, B, dim, k, okeys, odist, on, out_ids, s, sticky, timing};
+    return on_scratch(h, s, [&] { return search_plain(h, c, mode, ef, entry_key); });
 }
 
 int search_filtered_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int ef, int route,
                          const int32_t* filter_of, int64_t* okeys, float* odist, int32_t* on, hipStream_t s,
                          bool sticky) {
-    if (h->scr_valid && h->scr_stream != s) HIPCHK(h, hipStreamWaitEvent(s, h->scr_ev, 0));
-    const int r = search_filtered_body(h, queries, on_device, B, dim, k, ef, route, filter_of, okeys, odist, on, s, sticky);
-    HIPCHK(h, hipEventRecord(h->scr_ev, s));
-    h->scr_stream = s;
-    h->scr_valid = true;
-    return r;
+    SearchCall c{queries, on_device, B, dim, k, okeys, odist, on, nullptr, s, sticky, true};
+    return on_scratch(h, s, [&] { return search_filtered(h, c, ef, route, filter_of); });
 }
 
 }  // namespace mhh
@@ -654,12 +665,14 @@ int mhnsw_search_negatives(mhnsw_index* h, const float* queries, int64_t B, int 
         if (neg_count[b] < 0) return fail(h, MHNSW_EINVAL, "negative count %d for query %lld", neg_count[b], (long long)b);
         (neg_count[b] == 0 ? plain : rer).push_back(b);
     }
-    const int64_t ntot = [&] {
-        int64_t t = 0;
-        for (int64_t b = 0; b < B; ++b) t += neg_count[b];
-        return t;
-    }();
     hipStream_t s = h->stream;
+    auto scatter = [&](const std::vector<int64_t>& rows, const int64_t* kk, const float* ss, const int32_t* nn) {
+        for (size_t i = 0; i < rows.size(); ++i) {
+            memcpy(out_keys + (size_t)rows[i] * k, kk + i * k, (size_t)k * 8);
+            memcpy(out_score + (size_t)rows[i] * k, ss + i * k, (size_t)k * 4);
+            out_n[rows[i]] = nn[i];
+        }
+    };
     if (!plain.empty()) {
         std::vector<float> q(plain.size() * (size_t)dim);
         for (size_t i = 0; i < plain.size(); ++i)
@@ -670,23 +683,16 @@ int mhnsw_search_negatives(mhnsw_index* h, const float* queries, int64_t B, int 
         if ((r = search_impl(h, q.data(), false, (int64_t)plain.size(), dim, k, mode, ef, nullptr, kk.data(), dd.data(),
                              nn.data(), s, false)))
             return r;
-        for (size_t i = 0; i < plain.size(); ++i) {
-            memcpy(out_keys + (size_t)plain[i] * k, &kk[i * k], (size_t)k * 8);
-            memcpy(out_score + (size_t)plain[i] * k, &dd[i * k], (size_t)k * 4);
-            out_n[plain[i]] = nn[i];
-        }
+        scatter(plain, kk.data(), dd.data(), nn.data());
     }
     if (rer.empty()) return 0;
     const int64_t R = (int64_t)rer.size();
-    // gather the re-ranked queries and their negatives
-    std::vector<float> q((size_t)R * dim), ng((size_t)std::max<int64_t>(ntot, 1) * dim);
-    std::vector<int64_t> noff_b((size_t)B + 1, 0);
-    for (int64_t b = 0; b < B; ++b) noff_b[(size_t)b + 1] = noff_b[(size_t)b] + neg_count[b];
+    // gather the re-ranked queries; their negatives are `negatives` as given (the others have none)
+    std::vector<float> q((size_t)R * dim);
     int64_t w = 0;
     for (int64_t i = 0; i < R; ++i) {
         const int64_t b = rer[(size_t)i];
         memcpy(&q[(size_t)i * dim], queries + (size_t)b * dim, (size_t)dim * 4);
-        memcpy(&ng[(size_t)w * dim], negatives + (size_t)noff_b[(size_t)b] * dim, (size_t)neg_count[b] * dim * 4);
         w += neg_count[b];
         off.push_back((int32_t)w);
     }
@@ -700,7 +706,7 @@ int mhnsw_search_negatives(mhnsw_index* h, const float* queries, int64_t B, int 
     HIPCHK(h, hipMemcpyAsync(h->noff.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, s));
     if (w > 0) {
         if ((r = ensure_buf(h, h->tmp, (size_t)w * dim))) return r;
-        HIPCHK(h, hipMemcpyAsync(h->tmp.p, ng.data(), (size_t)w * dim * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->tmp.p, negatives, (size_t)w * dim * 4, hipMemcpyHostToDevice, s));
         LCHK(h, launch_pad_rows(h->tmp.p, w, dim, h->nneg.p, h->pitch, s));
     }
     // candidates: Search(near, kx) in the requested mode, internal ids kept
@@ -730,17 +736,9 @@ int mhnsw_search_negatives(mhnsw_index* h, const float* queries, int64_t B, int 
     HIPCHK(h, hipMemcpyAsync(kk.data(), h->nok.p, kk.size() * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(ss.data(), h->nos.p, ss.size() * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(nn.data(), h->non.p, nn.size() * 4, hipMemcpyDeviceToHost, s));
-    int err = 0;  // the candidate search and the re-ranking report into d_err[0]
-    HIPCHK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (err & 4) return fail(h, MHNSW_EINTERNAL, "out-of-range node id in adjacency (graph corrupt)");
-    if (err) return fail(h, MHNSW_EINTERNAL, "visited set overflow (raise vis_log2)");
-    for (int64_t i = 0; i < R; ++i) {
-        const int64_t b = rer[(size_t)i];
-        memcpy(out_keys + (size_t)b * k, &kk[(size_t)i * k], (size_t)k * 8);
-        memcpy(out_score + (size_t)b * k, &ss[(size_t)i * k], (size_t)k * 4);
-        out_n[b] = nn[(size_t)i];
-    }
+    // the candidate search and the re-ranking report into d_err[0]
+    if ((r = read_error(h, s))) return r;
+    scatter(rer, kk.data(), ss.data(), nn.data());
     return 0;
 }
 

@@ -498,17 +498,21 @@ class Graph:
         self._check(load().mhnsw_reserve(self._h, n, dim))
 
     # -- graph.go:534-625 / 1047-1110 --------------------------------------------
-    def search_arrays(self, queries, k: int, mode: int = MODE_COMPAT, ef: int = 0, entry_key: Optional[int] = None):
-        """Batched search, array form -> (keys int64[B,k], dist float32[B,k], n int32[B])."""
-        self._sync()
+    @staticmethod
+    def _search_io(queries, k: int):
+        """the query matrix of a host search and its three output arrays"""
         q = _f32(queries)
         if q.ndim == 1:
             q = q.reshape(1, -1)
-        B, d = q.shape
+        B = len(q)
         kk = max(int(k), 1)
-        ok = np.zeros((B, kk), np.int64)
-        od = np.zeros((B, kk), np.float32)
-        on = np.zeros(B, np.int32)
+        return q, np.zeros((B, kk), np.int64), np.zeros((B, kk), np.float32), np.zeros(B, np.int32)
+
+    def search_arrays(self, queries, k: int, mode: int = MODE_COMPAT, ef: int = 0, entry_key: Optional[int] = None):
+        """Batched search, array form -> (keys int64[B,k], dist float32[B,k], n int32[B])."""
+        self._sync()
+        q, ok, od, on = self._search_io(queries, k)
+        B, d = q.shape
         ek = None if entry_key is None else C.byref(C.c_int64(int(entry_key)))
         self._check(load().mhnsw_search(self._h, _ptr(q, C.c_float), B, d, int(k), mode, int(ef), ek,
                                         _ptr(ok, C.c_int64), _ptr(od, C.c_float), _ptr(on, C.c_int32)))
@@ -550,15 +554,9 @@ class Graph:
         (0: option filter_route) and keeps the max(ef, k) <= 128 best allowed
         rows; a route too narrow for the filter returns fewer than k."""
         self._sync()
-        q = _f32(queries)
-        if q.ndim == 1:
-            q = q.reshape(1, -1)
+        q, ok, od, on = self._search_io(queries, k)
         B, d = q.shape
         fo = np.ascontiguousarray(self._filter_ids(filters, B))
-        kk = max(int(k), 1)
-        ok = np.zeros((B, kk), np.int64)
-        od = np.zeros((B, kk), np.float32)
-        on = np.zeros(B, np.int32)
         self._check(load().mhnsw_search_filtered(self._h, _ptr(q, C.c_float), B, d, int(k), int(ef), int(route),
                                                  _ptr(fo, C.c_int32), _ptr(ok, C.c_int64), _ptr(od, C.c_float),
                                                  _ptr(on, C.c_int32)))
