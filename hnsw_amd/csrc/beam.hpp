@@ -404,11 +404,6 @@ template <class F>
 int beam_with_screen(const SearchArgs& a, F&& f) {
     return a.g.h16 ? f(std::true_type()) : f(std::false_type());
 }
-template <class K>
-int beam_launch(K kernel, int64_t grid, int block, int lds_words, const SearchArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), (size_t)4 * (size_t)lds_words, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
 
 // the layer-0 launch over list LT
 template <class C, class LT, int G, int XW>
@@ -423,30 +418,20 @@ static int launch_beam_t(const SearchArgs& a, hipStream_t s) {
         // kernel at every batch size)
         if constexpr (XW == 1 && R >= 1) {
             if (R <= 2 && beam_small_batch(a) && !a.order)
-                return beam_launch(k_search_beam_mw<C, R, G, SC>, a.B, 64 * BMW_WAVES, lds, a, s);
+                return launch_grid(k_search_beam_mw<C, R, G, SC>, a.B, 64 * BMW_WAVES, lds, a, s);
         }
         const int64_t grid = a.order ? beam_order_grid(a) : a.B;
         if constexpr (R == 0)
-            return beam_launch(k_search_beam_lds<C, G, SC, XW>, grid, 64, lds, a, s);
+            return launch_grid(k_search_beam_lds<C, G, SC, XW>, grid, 64, lds, a, s);
         else
-            return beam_launch(k_search_beam<C, R, G, SC, XW>, grid, 64, lds, a, s);
+            return launch_grid(k_search_beam<C, R, G, SC, XW>, grid, 64, lds, a, s);
     });
-}
-
-// group width G of configuration (L, V), from MH_FOR_EACH_CFG
-template <int L, int V>
-constexpr int beam_group() {
-#define X_(L_, V_, G_) \
-    if (L == L_ && V == V_) return G_;
-    MH_FOR_EACH_CFG(X_)
-#undef X_
-    return 0;
 }
 
 template <int L, int V, int XW>
 int launch_beam_cfg(const SearchArgs& a, hipStream_t s) {
     using C = Cfg<L, V>;
-    constexpr int G = beam_group<L, V>();
+    constexpr int G = cfg_group<L, V>();
     if (const int rc = beam_limits(a, false)) return rc;
     const int efl = beam_efl(a);
     if (efl <= 64) return launch_beam_t<C, BList<1>, G, XW>(a, s);
@@ -459,7 +444,7 @@ int launch_beam_cfg(const SearchArgs& a, hipStream_t s) {
 template <int L, int V, int XW>
 int launch_beam_lds_cfg(const SearchArgs& a, hipStream_t s) {
     if (const int rc = beam_limits(a, true)) return rc;
-    return launch_beam_t<Cfg<L, V>, LList, beam_group<L, V>(), XW>(a, s);
+    return launch_beam_t<Cfg<L, V>, LList, cfg_group<L, V>(), XW>(a, s);
 }
 
 // the filtered launch: beam_limits over the route width
@@ -469,7 +454,7 @@ int launch_beam_filt_cfg(const SearchArgs& a, const FilterArgs& f, hipStream_t s
     if (const int rc = beam_limits(a, true)) return rc;
     const int lds = beam_lds<LList>(a).words;
     return beam_with_screen(a, [&](auto screen) {
-        hipLaunchKernelGGL((k_search_beam_filt<Cfg<L, V>, beam_group<L, V>(), decltype(screen)::value>),
+        hipLaunchKernelGGL((k_search_beam_filt<Cfg<L, V>, cfg_group<L, V>(), decltype(screen)::value>),
                            dim3((unsigned)a.B), dim3(64), (size_t)4 * (size_t)lds, s, a, f);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     });
@@ -482,7 +467,7 @@ int launch_beam_descend_cfg(const SearchArgs& a, hipStream_t s) {
     if (const int rc = beam_limits(a, beam_in_lds(a))) return rc;
     const int lds = beam_lds<BList<1>>(a).words;  // (the visited set alone)
     return beam_with_screen(a, [&](auto screen) {
-        return beam_launch(k_beam_descend<Cfg<L, V>, beam_group<L, V>(), decltype(screen)::value>, a.B, 64, lds, a, s);
+        return launch_grid(k_beam_descend<Cfg<L, V>, cfg_group<L, V>(), decltype(screen)::value>, a.B, 64, lds, a, s);
     });
 }
 

@@ -1,5 +1,5 @@
 // device_search.hpp -- per-wave layer searches shared by the search kernels
-// (search.hip) and the build kernels (build.hip).
+// (search.hip) and the build kernels (build_compat.hpp, build_batch.hpp).
 //
 //   beam_layer   : sorted-list best-first search (standard HNSW Alg. 2 stop
 //                  rule), restated in oracle/oracle.c beam_layer_search.
@@ -251,10 +251,10 @@ __device__ __forceinline__ void wave_sync() {
 // How the sequential (compat) walks evaluate distances and order their own
 // lanes.  WaveEval: everything on the calling wave (a 64-thread workgroup, so
 // __syncthreads only orders this wave).  The multi-wave build evaluator
-// (build.hip MwEval) has the same interface and spreads each batch of rows
+// (build_compat.hpp MwEval) has the same interface and spreads each batch of rows
 // over the workgroup's other waves.
 struct WaveEval {
-    static constexpr bool kPairs = false;  // no batched per-row scoring (build.hip MwEval::pairs)
+    static constexpr bool kPairs = false;  // no batched per-row scoring (build_compat.hpp MwEval::pairs)
     uint32_t* list = nullptr;  // LDS candidate list (run_list)
     template <class C, int G, class Sink>
     __device__ __forceinline__ void run(const GraphDev& g, const QReg<C>& q, float qn, uint32_t cid, int cnt,

@@ -1,5 +1,5 @@
 // engine.hpp -- host-side launch interface between the C ABI (api.cpp) and the
-// HIP kernels (search.hip, build.hip, exact.hip).  No torch types anywhere.
+// HIP kernels (search.hip, build.hip, exact.hip and the *_units.hip).  No torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,9 +30,9 @@ inline int pitch_of(int lpr, int vpl) { return lpr * 4 * vpl; }
 
 // The same configurations as X(lpr, vpl, G), for the code that instantiates or
 // selects a kernel per configuration.  G: the group width, rows in flight per
-// wave step.  In four groups: the units of beam_units.hip and walks_units.hip
-// each instantiate one or two of them, so that they compile in parallel.
-// (build.hip compiles in parts, each with its own statement of its group.)
+// wave step.  In four groups: the units of beam_units.hip, walks_units.hip and
+// build_units.hip each instantiate one or two of them, so that they compile in
+// parallel.
 #define MH_CFGS_A(X) X(16, 1, 2) X(32, 1, 4) X(64, 1, 8)
 #define MH_CFGS_B(X) X(64, 2, 8) X(64, 3, 8)
 #define MH_CFGS_C(X) X(64, 4, 4) X(64, 6, 4)
@@ -51,6 +51,22 @@ int with_cfg(int lpr, int vpl, F&& f) {
     MH_FOR_EACH_CFG(X_)
 #undef X_
     return -3;
+}
+// group width G of configuration (L, V), from the table (0: not in it)
+template <int L, int V>
+constexpr int cfg_group() {
+#define X_(L_, V_, G_) \
+    if (L == L_ && V == V_) return G_;
+    MH_FOR_EACH_CFG(X_)
+#undef X_
+    return 0;
+}
+
+// one launch of a kernel that takes the argument struct `a`: grid workgroups, lds_words 32-bit words of dynamic LDS
+template <class K, class A>
+int launch_grid(K kernel, int64_t grid, int block, int lds_words, const A& a, hipStream_t s) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), (size_t)4 * (size_t)lds_words, s, a);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 struct SearchArgs {
@@ -197,7 +213,7 @@ struct BatchBuildArgs {
     int mcap;                     // neighbors to select on this layer
     int heuristic;                // 0 closest-M, 1 HNSW heuristic on the new row, 2 also on overflowing rows
     int keep_pruned;              // fill the new row with pruned candidates up to mcap
-    int expand;                   // entries expanded per step of the layer search (1 or 2; beam_layer XW)
+    int expand;                   // entries expanded per step of the layer search (1-4; beam_layer XW)
     float alpha;                  // diversity slack: drop c when alpha * d(c, kept) < d(u, c) (1 = HNSW Alg. 4)
     int32_t* inc_cnt;             // [cap_nodes] incoming request counters (zero between batches)
     uint32_t* inc_src;            // [cap_nodes * inc_cap]

@@ -153,12 +153,12 @@ static int launch_compat_t(const SearchArgs& a, hipStream_t s) {
 
 template <int L, int V>
 int launch_compat_cfg(const SearchArgs& a, hipStream_t s) {
-    return launch_compat_t<Cfg<L, V>, beam_group<L, V>()>(a, s);
+    return launch_compat_t<Cfg<L, V>, cfg_group<L, V>()>(a, s);
 }
 
 template <int L, int V>
 int launch_negatives_cfg(const NegArgs& a, hipStream_t s) {
-    constexpr int G = beam_group<L, V>();
+    constexpr int G = cfg_group<L, V>();
     hipLaunchKernelGGL((k_negatives<Cfg<L, V>, (G < 4 ? G : 4)>), dim3((unsigned)a.B), dim3(64), 0, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

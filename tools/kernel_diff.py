@@ -3,8 +3,11 @@ of two trees built with the same flags): for every gfx950 kernel symbol the
 instruction count, VGPRs, SGPRs, static LDS and scratch from the code object's
 metadata, and whether the disassembly (addresses and encodings stripped) is
 identical.  The record of a change that must leave the existing kernels as they
-were (profiles/filtered_search_build.txt).
-Usage: python tools/kernel_diff.py PARENT_OBJ_DIR BRANCH_OBJ_DIR [unit-glob]"""
+were (profiles/filtered_search_build.txt).  Objects are paired by file name;
+with --pool the kernels of every object of each directory go into one table and
+are paired by symbol, for a change that moves kernels between objects
+(profiles/build_refactor.txt); symbols found on one side only are listed.
+Usage: python tools/kernel_diff.py [--pool] PARENT_OBJ_DIR BRANCH_OBJ_DIR [unit-glob]"""
 import collections
 import glob
 import os
@@ -30,7 +33,8 @@ def code_object(obj, tmp):
                               text=True, check=True).stdout
     if ".hip_fatbin" not in sections:
         raise HostOnly(obj)
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj],
+    # (with an output named: llvm-objcopy otherwise rewrites the object in place, which make then takes for new)
+    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj, fat + ".o"],
                           stderr=subprocess.DEVNULL)
     subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=" + TARGET,
                            "--input=" + fat, "--output=" + out, "--unbundle"], stderr=subprocess.DEVNULL)
@@ -48,7 +52,7 @@ def kernels(co):
             cur = m.group(1)
             continue
         t = line.strip()
-        if cur and t and not t.startswith("//"):
+        if cur and t and not t.startswith("//") and t != "...":  # ("...": zero padding after the kernel's code)
             t = re.sub(r"\s*//.*$", "", t)        # (the address comment)
             t = re.sub(r"<[^>]*>", "<L>", t)      # (branch targets by label text)
             body[cur].append(t)
@@ -80,48 +84,81 @@ def template_of(sym):
     return m.group(1) if m else sym
 
 
+def compare(name, ka, kb, tot, per, list_single=False):
+    """count the kernels of two symbol tables, print the differing ones (and,
+    list_single, the symbols found on one side only)"""
+    for s in sorted(set(ka) | set(kb)):
+        t = template_of(s)
+        if s not in ka or s not in kb:
+            side = "only parent" if s in ka else "only branch"
+            per[t][side] += 1
+            tot[side] += 1
+            if list_single:
+                print(f"{side.upper()} {name} {s}")
+            continue
+        per[t]["kernels"] += 1
+        tot["kernels"] += 1
+        if ka[s] != kb[s]:
+            per[t]["differing"] += 1
+            tot["differing"] += 1
+            print(f"DIFF {name} {s}: instructions {len(ka[s][0])} -> {len(kb[s][0])}, metadata {ka[s][1]} -> {kb[s][1]}")
+        if ka[s][1].get("private_segment_fixed_size", 0) or kb[s][1].get("private_segment_fixed_size", 0):
+            tot["with scratch"] += 1
+
+
+def pool(obj_dir, pat, tmp):
+    """the kernels of every object of a directory in one table; a symbol that
+    two objects hold must be the same kernel in both"""
+    out = {}
+    for p in sorted(glob.glob(os.path.join(obj_dir, pat))):
+        try:
+            ks = kernels(code_object(p, tmp))
+        except HostOnly:
+            continue
+        for s, k in ks.items():
+            if s in out and out[s] != k:
+                sys.exit(f"{obj_dir}: {s} differs between two objects (one of them {os.path.basename(p)})")
+            out[s] = k
+    return out
+
+
 def main():
-    a_dir, b_dir = sys.argv[1], sys.argv[2]
-    pat = sys.argv[3] if len(sys.argv) > 3 else "*.o"
-    units = sorted(os.path.basename(p) for p in glob.glob(os.path.join(a_dir, pat)))
+    args = [a for a in sys.argv[1:] if a != "--pool"]
+    pooled = len(args) != len(sys.argv) - 1
+    a_dir, b_dir = args[0], args[1]
+    pat = args[2] if len(args) > 2 else "*.o"
     tot = collections.Counter()
     per = collections.defaultdict(collections.Counter)
     with tempfile.TemporaryDirectory() as tmp:
-        for u in units:
-            if not os.path.exists(os.path.join(b_dir, u)):
-                print(f"{u}: only in parent")
-                continue
-            try:
-                ka = kernels(code_object(os.path.join(a_dir, u), tmp))
-                kb = kernels(code_object(os.path.join(b_dir, u), tmp))
-            except HostOnly:
-                continue
-            for s in sorted(set(ka) | set(kb)):
-                t = template_of(s)
-                if s not in ka or s not in kb:
-                    per[t]["only parent" if s in ka else "only branch"] += 1
+        if pooled:
+            ka, kb = pool(a_dir, pat, tmp), pool(b_dir, pat, tmp)
+            print(f"kernels: parent {len(ka)}, branch {len(kb)}")
+            compare("(pooled)", ka, kb, tot, per, list_single=True)
+        else:
+            units = sorted(os.path.basename(p) for p in glob.glob(os.path.join(a_dir, pat)))
+            for u in units:
+                if not os.path.exists(os.path.join(b_dir, u)):
+                    print(f"{u}: only in parent")
                     continue
-                per[t]["kernels"] += 1
-                tot["kernels"] += 1
-                same = ka[s][0] == kb[s][0] and ka[s][1] == kb[s][1]
-                if not same:
-                    per[t]["differing"] += 1
-                    tot["differing"] += 1
-                    print(f"DIFF {u} {s}: instructions {len(ka[s][0])} -> {len(kb[s][0])}, metadata {ka[s][1]} -> {kb[s][1]}")
-                if ka[s][1].get("private_segment_fixed_size", 0) or kb[s][1].get("private_segment_fixed_size", 0):
-                    tot["with scratch"] += 1
-        for u in sorted(os.path.basename(p) for p in glob.glob(os.path.join(b_dir, pat))):
-            if u not in units:
                 try:
-                    kb = kernels(code_object(os.path.join(b_dir, u), tmp))
+                    compare(u, kernels(code_object(os.path.join(a_dir, u), tmp)),
+                            kernels(code_object(os.path.join(b_dir, u), tmp)), tot, per)
                 except HostOnly:
                     continue
-                tot["new"] += len(kb)
-                print(f"{u}: only in branch, {len(kb)} kernels")
-                for s, (ins, md) in sorted(kb.items()):
-                    print(f"  NEW {s}: {len(ins)} instructions, {md}")
+            for u in sorted(os.path.basename(p) for p in glob.glob(os.path.join(b_dir, pat))):
+                if u not in units:
+                    try:
+                        kb = kernels(code_object(os.path.join(b_dir, u), tmp))
+                    except HostOnly:
+                        continue
+                    tot["new"] += len(kb)
+                    print(f"{u}: only in branch, {len(kb)} kernels")
+                    for s, (ins, md) in sorted(kb.items()):
+                        print(f"  NEW {s}: {len(ins)} instructions, {md}")
     print(f"compared {tot['kernels']} kernels: identical ISA and metadata {tot['kernels'] - tot['differing']}, "
           f"differing {tot['differing']}; kernels with scratch > 0 (either side): {tot['with scratch']}")
+    if pooled:
+        print(f"symbols only in parent {tot['only parent']}, only in branch {tot['only branch']}")
     print("per kernel template: kernels / differing")
     for t in sorted(per):
         extra = "".join(f", {k} {v}" for k, v in per[t].items() if k.startswith("only"))
