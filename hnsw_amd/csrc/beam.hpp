@@ -43,8 +43,9 @@ __host__ __device__ inline int beam_vis_words(const SearchArgs& a) { return a.vi
 // less than the vis_n words of the 32-bit set, which the compact set leaves
 // partly unused (the default compact set with the scratch fits the 20 KiB a
 // 2-wave SIMD allows).  The host sets vis16 only with vis_n >= VIS16_WORDS
-// (search_host.cpp), so for the lists that do not merge, and for the pre-pass,
-// this is vis_n itself.  LDS: the list, 16-byte aligned.
+// (search_host.cpp), so for the lists that do not merge, and for a pre-pass
+// that keeps the launch's set (beam_desc_vis), this is vis_n itself.  LDS: the
+// list, 16-byte aligned.
 struct BeamLds {
     int list, words;
 };
@@ -327,13 +328,77 @@ __global__ __launch_bounds__(64 * BMW_WAVES) void k_search_beam_mw(SearchArgs a)
 
 // ---------------------------------------------------------------------------
 // ordered path, pre-pass: the descent through the layers top .. beam_order_lo
-// alone, one wave per query, with the fused kernels' upper_ef, visited set and
-// screen.  Writes the node it stopped on, the sort key of the descent path and
-// the sort's value (the query's index); its counters go into the same slots as
-// the layer-0 launch's, which walks the remaining layers.
+// alone, one wave per query, with the fused kernels' upper_ef and screen.
+// Writes the node it stopped on, the sort key of the descent path and the
+// sort's value (the query's index).
+//
+// A descent is a chain of dependent round trips -- per layer the deg check and
+// the entry's row, per expansion the adjacency row, the fp16 screen and the f32
+// survivors -- and nothing hides it but other waves.  So the pre-pass is shaped
+// for waves in flight, not for rows in flight (DESIGN.md "Query order", the
+// pre-pass; measured at the headline's Cfg<64, 3>):
+//  - rows in flight and registers: beam_desc_group / beam_desc_waves below, not
+//    the layer-0 search's cfg_group.  Every distance is the same sum whatever G
+//    (eval_rows: the lane's partial sum, then reduce_rows' one butterfly).
+//  - the visited set: beam_desc_vis entries, passed as `pvis` (the size the
+//    launch asked LDS for), not the layer-0 search's a.vis_n / a.vis16.
+//  - the counters: E, X, S and F go to a.pstat, one store per query, and
+//    k_beam_descend_stats (search.hip) adds them up into the slots the layer-0
+//    launch uses; 65,536 waves' atomicAdd on the same words within a millisecond
+//    queue on them (0.7 ms of the step at the headline).  A visited reset, which
+//    a pre-pass hardly ever sees, is still counted where it happens.
 // ---------------------------------------------------------------------------
-template <class C, int G, bool SCREEN>
-__global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_beam_descend(SearchArgs a) {
+// MH_DESC_G / MH_DESC_WAVES / MH_DESC_VIS (build flags, for tools/ variants):
+// another G, waves per SIMD or visited-set size for every configuration's pre-pass
+// (0 = the rule)
+#ifndef MH_DESC_G
+#define MH_DESC_G 0
+#endif
+#ifndef MH_DESC_WAVES
+#define MH_DESC_WAVES 0
+#endif
+#ifndef MH_DESC_VIS
+#define MH_DESC_VIS 0
+#endif
+// Rows in flight per wave step, and the waves per SIMD the compiler must fit.
+// At the headline, screened: G 8 takes 213 VGPRs (2 waves), G 4 139 (3), G 2
+// 105 (4), G 1 89 (5); 4 waves of G 2 and 5 of G 1 run the pre-pass equally fast
+// (a narrower G takes more round trips per expansion), both ahead of G 4, and a
+// target that makes the compiler spill (G 4 at 4 waves, G 2 at 6 or 8) is slower
+// than the same G without it.  The rule for every configuration: G at most 2, and
+// the 4 waves where the screened kernel fits their 128 registers without scratch
+// (rows of up to 4 float4 per lane), else the 2 of the layer-0 kernels.
+template <int L, int V>
+constexpr int beam_desc_group() {
+    constexpr int G = cfg_group<L, V>();
+    return MH_DESC_G > 0 ? (MH_DESC_G < G ? MH_DESC_G : G) : G < 2 ? G : 2;
+}
+template <int L, int V>
+constexpr int beam_desc_waves() {
+    return MH_DESC_WAVES > 0 ? MH_DESC_WAVES : V <= 4 ? 4 : 2;
+}
+// The visited set: a greedy walk (upper_ef 1) probes a few tens of ids per layer
+// and a walk with a list of 4 a few hundred at most, and the set is cleared at
+// every layer, so up to upper_ef 4 the pre-pass takes 1,024 entries (4 KiB)
+// instead of the layer-0 search's 5,120 (20 KiB, which alone held the pre-pass
+// to 2 waves per SIMD).  It resets at 768 ids in ONE layer, that is after 48
+// expansions of 16 neighbours there: the headline's pre-pass expands 11 nodes
+// and evaluates 114 rows per query over ALL its layers (and the tests compare
+// the counters with the fused launch's, resets included).  A pathological
+// single-layer walk past it adds a
+// reset the fused launch does not have, which changes the counters and never
+// the lists.  A wider
+// upper_ef, or a set the user made no larger than this, keeps the launch's own
+// set.  0: the launch's own.
+constexpr int BEAM_DESC_VIS = 1024, BEAM_DESC_VIS_MAX_EF = 4;
+inline int beam_desc_vis(const SearchArgs& a) {
+    const int n = MH_DESC_VIS > 0 ? MH_DESC_VIS : BEAM_DESC_VIS;
+    return a.upper_ef <= BEAM_DESC_VIS_MAX_EF && beam_vis_words(a) > n ? n : 0;
+}
+
+template <class C, int G, bool SCREEN, int W>
+__global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_eu(W))) void k_beam_descend(SearchArgs a,
+                                                                                                            int pvis) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int64_t b = blockIdx.x;
     if (b >= a.B) return;
@@ -341,7 +406,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_beam_desc
     load_query(q, a.q + (size_t)b * C::PITCH);
     const float qn = query_norm(q);
     WaveStats st;
-    const int vsz = a.vis16 ? -1 : a.vis_n;
+    const int vsz = pvis > 0 ? pvis : a.vis16 ? -1 : a.vis_n;
     unsigned long long key = 0;
     const uint32_t ep =
         beam_descend<C, G, SCREEN, true>(a, q, qn, smem, vsz, st, WaveBatch(), a.entry, a.top, beam_order_lo(a), false, &key);
@@ -349,8 +414,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_beam_desc
         a.ep0[b] = ep;
         a.okey[b] = key;
         a.oidx[b] = (uint32_t)b;
+        // (a descent's counts are far below 2^32)
+        reinterpret_cast<uint4*>(a.pstat)[b] = make_uint4((uint32_t)st.E, (uint32_t)st.X, (uint32_t)st.S, (uint32_t)st.F);
+        if (st.resets) atomicAdd(&a.stats[2], st.resets);
     }
-    beam_stats(a, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -465,9 +532,12 @@ int launch_beam_filt_cfg(const SearchArgs& a, const FilterArgs& f, hipStream_t s
 template <int L, int V>
 int launch_beam_descend_cfg(const SearchArgs& a, hipStream_t s) {
     if (const int rc = beam_limits(a, beam_in_lds(a))) return rc;
-    const int lds = beam_lds<BList<1>>(a).words;  // (the visited set alone)
+    const int pvis = beam_desc_vis(a);
+    const int lds = pvis > 0 ? pvis : beam_lds<BList<1>>(a).words;  // (the visited set alone)
     return beam_with_screen(a, [&](auto screen) {
-        return launch_grid(k_beam_descend<Cfg<L, V>, cfg_group<L, V>(), decltype(screen)::value>, a.B, 64, lds, a, s);
+        hipLaunchKernelGGL((k_beam_descend<Cfg<L, V>, beam_desc_group<L, V>(), decltype(screen)::value, beam_desc_waves<L, V>()>),
+                           dim3((unsigned)a.B), dim3(64), (size_t)4 * (size_t)lds, s, a, pvis);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
     });
 }
 

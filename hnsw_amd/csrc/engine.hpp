@@ -99,6 +99,8 @@ struct SearchArgs {
     uint32_t* ep0 = nullptr;             // [B] the node each query's pre-pass stopped on (beam.hpp beam_order_lo)
     unsigned long long* okey = nullptr;  // [B] sort key: the descent's nodes of layers key_top .. key_top - key_n + 1
     uint32_t* oidx = nullptr;            // [B] 0 .. B - 1 (the sort's values)
+    uint32_t* pstat = nullptr;           // [4 * B], 16-byte aligned: each query's pre-pass counters (E, X, S, F),
+                                         // summed into stats after the pre-pass (search.hip k_beam_descend_stats)
     int key_top = 0, key_n = 0;          // the layers in the key (key_n = 0: every key is 0)
     int key_id_bits = 1;                 // bits per field of the key (in [1, 31])
     int key_hash = 0;                    // the fields are narrower than a node id: they hold a hash of it

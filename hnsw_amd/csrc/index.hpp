@@ -156,7 +156,8 @@ struct mhnsw_index {
     DevBuf<int64_t> okeys;
     DevBuf<float> odist;
     DevBuf<int32_t> on;
-    // ordered beam search: sort keys in / out [2 B], {query index, order, layer-0 entry} [3 B], sort scratch
+    // ordered beam search: sort keys in / out [2 B], {query index, order, layer-0 entry} [3 B] and the pre-pass's
+    // counters per query [4 B], sort scratch
     DevBuf<unsigned long long> ordkey;
     DevBuf<uint32_t> ordval;
     DevBuf<uint8_t> ordtmp;

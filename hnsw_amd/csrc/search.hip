@@ -429,9 +429,34 @@ int launch_search_beam_filtered(const SearchArgs& a, const FilterArgs& f, int lp
     return with_cfg(lpr, vpl, [&](auto c) { return launch_beam_filt_cfg<c.L, c.V>(a, f, s); });
 }
 
+// The pre-pass's counters: k_beam_descend leaves each query's E, X, S and F in
+// a.pstat, and this adds them up into the slots the layer-0 launch adds to
+// (beam.hpp beam_stats), a few hundred atomicAdd instead of four per query.
+constexpr int DESC_STATS_BLOCKS = 64;
+__global__ __launch_bounds__(256) void k_beam_descend_stats(SearchArgs a) {
+    unsigned long long t[4] = {0, 0, 0, 0};
+    for (int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x; b < a.B; b += (int64_t)gridDim.x * 256) {
+        const uint4 v = reinterpret_cast<const uint4*>(a.pstat)[b];
+        t[0] += v.x;
+        t[1] += v.y;
+        t[2] += v.z;
+        t[3] += v.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        for (int o = 32; o >= 1; o >>= 1) t[i] += __shfl_xor(t[i], o, 64);
+    if (lane_id() == 0) {
+        atomicAdd(&a.stats[0], t[0]);
+        atomicAdd(&a.stats[1], t[1]);
+        atomicAdd(&a.stats[8], t[2]);
+        atomicAdd(&a.stats[9], t[3]);
+    }
+}
+
 int launch_beam_descend(const SearchArgs& a, int lpr, int vpl, hipStream_t s) {
     if (a.B <= 0) return 0;
-    return with_cfg(lpr, vpl, [&](auto c) { return launch_beam_descend_cfg<c.L, c.V>(a, s); });
+    if (const int rc = with_cfg(lpr, vpl, [&](auto c) { return launch_beam_descend_cfg<c.L, c.V>(a, s); })) return rc;
+    return launch_grid(k_beam_descend_stats, std::min<int64_t>(DESC_STATS_BLOCKS, (a.B + 255) / 256), 256, 0, a, s);
 }
 
 int launch_negatives(const NegArgs& a, int lpr, int vpl, hipStream_t s) {

@@ -216,12 +216,14 @@ static int beam_search(mhnsw_index* h, const SearchCall& c, SearchArgs& a) {
     size_t tmp_bytes = 0;
     if (ordered) {
         LCHK(h, order_sort_temp_bytes(B, &tmp_bytes));
-        if ((r = ensure_buf(h, h->ordkey, (size_t)2 * B)) || (r = ensure_buf(h, h->ordval, (size_t)3 * B)) ||
+        const size_t pstat_at = ((size_t)3 * B + 3) & ~(size_t)3;  // (16-byte aligned: one store per query)
+        if ((r = ensure_buf(h, h->ordkey, (size_t)2 * B)) || (r = ensure_buf(h, h->ordval, pstat_at + (size_t)4 * B)) ||
             (r = ensure_buf(h, h->ordtmp, std::max<size_t>(tmp_bytes, 1))))
             return r;
         a.okey = h->ordkey.p;
         a.oidx = h->ordval.p;
         a.ep0 = h->ordval.p + 2 * B;
+        a.pstat = h->ordval.p + pstat_at;
         order_key_layers(h, B, a.top, a);
         a.order_chunk = h->search_order_map == 0 ? (B + 7) / 8 : 0;
     }
