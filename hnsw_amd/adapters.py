@@ -75,6 +75,21 @@ class ExactIndex:
         ok, od, on = self._g.search_arrays(np.asarray(queries, np.float32), k, mode=MODE_EXACT)
         return [self._g.decode_keys(ok[b, : on[b]]) for b in range(len(on))], od, on
 
+    def Filter(self, keys=()):
+        """An allow-list of the present keys among `keys` (Graph.Filter) for SearchFiltered."""
+        return self._g.Filter(keys)
+
+    def SearchFiltered(self, query, k: int, filter) -> List[Node]:
+        """Search among the filter's keys only: the brute force over the allowed rows."""
+        if self.Len() == 0:
+            return []
+        return self._g.SearchFiltered(np.asarray(query, np.float32), k, filter, mode=MODE_EXACT)
+
+    def search_filtered_batch(self, queries, k: int, filters) -> Tuple[list, np.ndarray, np.ndarray]:
+        """Batched form (one Filter, or one per query; None: every key) -> as search_batch."""
+        ok, od, on = self._g.search_filtered_arrays(np.asarray(queries, np.float32), k, filters, mode=MODE_EXACT)
+        return [self._g.decode_keys(ok[b, : on[b]]) for b in range(len(on))], od, on
+
     def Delete(self, key) -> bool:  # exact.go:112-124
         return self._g.Delete(key)
 
@@ -151,6 +166,13 @@ class ExactAdapter:
         if self.index.Len() == 0:
             return [], []
         ks, od, on = self.index.search_batch(np.asarray(query, np.float32).reshape(1, -1), k)
+        return ks[0], od[0, : on[0]].tolist()
+
+    def SearchFiltered(self, query, k: int, filter) -> Tuple[list, List[float]]:
+        """Search among the keys of an ExactIndex.Filter."""
+        if self.index.Len() == 0:
+            return [], []
+        ks, od, on = self.index.search_filtered_batch(np.asarray(query, np.float32).reshape(1, -1), k, filter)
         return ks[0], od[0, : on[0]].tolist()
 
     def Delete(self, key) -> bool:

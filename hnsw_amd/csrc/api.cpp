@@ -1067,6 +1067,9 @@ int mhnsw_create(int metric, int M, double ml, int ef_search, uint64_t seed, mhn
         hipMalloc(&h->d_layer_entry, 3 * MH_MAXL * 4) != hipSuccess ||
         hipMalloc(&h->d_layers, MH_MAXL * sizeof(LayerDev)) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess ||
         hipEventCreate(&h->ev1) != hipSuccess || hipEventCreate(&h->gev0) != hipSuccess ||
+        hipEventCreate(&h->fxev[0]) != hipSuccess || hipEventCreate(&h->fxev[1]) != hipSuccess ||
+        hipEventCreate(&h->fxev[2]) != hipSuccess || hipEventCreate(&h->fxev[3]) != hipSuccess ||
+        hipEventCreate(&h->fxev[4]) != hipSuccess || hipEventCreate(&h->fxev[5]) != hipSuccess ||
         hipEventCreate(&h->gev1) != hipSuccess || hipEventCreateWithFlags(&h->scr_ev, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->meta_ev, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ord_ev, hipEventDisableTiming) != hipSuccess || hipMemset(h->d_stats, 0, 16 * sizeof(unsigned long long)) != hipSuccess) {
@@ -1158,6 +1161,15 @@ void mhnsw_destroy(mhnsw_index* h) {
     drop_filters(h);
     F(h->d_filters);
     F(h->fof.p);
+    F(h->fxwords.p);
+    F(h->fxcnt.p);
+    F(h->fxids.p);
+    F(h->fxmask.p);
+    F(h->fxplane.p);
+    F(h->fxinv.p);
+    F(h->fxnorm.p);
+    for (auto e : h->fxev)
+        if (e) (void)hipEventDestroy(e);
     if (h->scr_ev) (void)hipEventDestroy(h->scr_ev);
     if (h->meta_ev) (void)hipEventDestroy(h->meta_ev);
     if (h->ord_ev) (void)hipEventDestroy(h->ord_ev);
@@ -1388,6 +1400,16 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
             return MHNSW_EINVAL;
         *v = (int64_t)std::llround((double)ms * 1e6);
     }
+    else if (n.rfind("last_fx_", 0) == 0) {  // read-only: the last filtered exact search's stages (HIP events)
+        static const char* const stage[5] = {"compact", "gather", "select", "rerank", "fallback"};
+        int i = 0;
+        while (i < 5 && n != std::string("last_fx_") + stage[i] + "_ns") ++i;
+        float ms = 0.f;
+        if (i == 5 || !h->have_fx_timing || hipEventSynchronize(h->fxev[i + 1]) != hipSuccess ||
+            hipEventElapsedTime(&ms, h->fxev[i], h->fxev[i + 1]) != hipSuccess)
+            return MHNSW_EINVAL;
+        *v = (int64_t)std::llround((double)ms * 1e6);
+    }
     else if (n == "screen_err_ppb") {  // read-only: the fp16 copy's measured margin E, parts per 1e9
         float e = 0.f;
         if (h->h16err && (hipMemcpyAsync(&e, h->h16err, sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
@@ -1548,6 +1570,53 @@ int mhnsw_search_filtered_device(mhnsw_index* h, const float* d_queries, int64_t
     std::unique_lock<std::shared_mutex> lk(h->mu);
     return search_filtered_impl(h, d_queries, true, B, dim, k, ef, route, d_filter_of, d_keys, d_dist, d_n,
                                 (hipStream_t)stream, true);
+}
+
+// The batch by filter: one pass per distinct filter id (ascending), a pass's queries gathered
+// and its results scattered to the callers' positions (a batch of one filter runs in place).
+int mhnsw_search_filtered_exact(mhnsw_index* h, const float* queries, int64_t B, int dim, int k, const int32_t* filter_of,
+                                int64_t* out_keys, float* out_dist, int32_t* out_n) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    if (B > 0 && !filter_of) return fail(h, MHNSW_EINVAL, "filter_of must be non-NULL");
+    std::map<int32_t, std::vector<int64_t>> groups;
+    for (int64_t b = 0; b < B; ++b) groups[filter_of[b]].push_back(b);
+    if (groups.size() <= 1)
+        return search_filtered_exact_impl(h, queries, false, B, dim, k, B > 0 ? filter_of[0] : -1, out_keys, out_dist,
+                                          out_n, h->stream, false);
+    // every argument error before the first pass writes a result
+    if (k <= 0) return fail(h, MHNSW_EK, "k must be greater than 0, got %d", k);
+    if (k > 256) return fail(h, MHNSW_EUNSUPPORTED, "exact mode supports k <= 256");
+    for (const auto& [f, rows] : groups)
+        if (f < -1 || (f >= 0 && (f >= (int)h->filters.size() || !h->filters[f].used)))
+            return fail(h, MHNSW_EINVAL, "unknown filter %d", f);
+    std::vector<float> q;
+    std::vector<int64_t> kk;
+    std::vector<float> dd;
+    std::vector<int32_t> nn;
+    for (const auto& [f, rows] : groups) {
+        const size_t R = rows.size();
+        q.resize(R * (size_t)dim);
+        kk.resize(R * (size_t)k);
+        dd.resize(R * (size_t)k);
+        nn.assign(R, 0);
+        for (size_t i = 0; i < R; ++i) memcpy(&q[i * dim], queries + (size_t)rows[i] * dim, (size_t)dim * 4);
+        if (int r = search_filtered_exact_impl(h, q.data(), false, (int64_t)R, dim, k, f, kk.data(), dd.data(), nn.data(),
+                                               h->stream, false))
+            return r;
+        for (size_t i = 0; i < R; ++i) {
+            memcpy(out_keys + (size_t)rows[i] * k, &kk[i * k], (size_t)k * 8);
+            memcpy(out_dist + (size_t)rows[i] * k, &dd[i * k], (size_t)k * 4);
+            out_n[rows[i]] = nn[i];
+        }
+    }
+    return MHNSW_OK;
+}
+
+int mhnsw_search_filtered_exact_device(mhnsw_index* h, const float* d_queries, int64_t B, int dim, int k, int filter,
+                                       int64_t* d_keys, float* d_dist, int32_t* d_n, void* stream) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    return search_filtered_exact_impl(h, d_queries, true, B, dim, k, filter, d_keys, d_dist, d_n, (hipStream_t)stream,
+                                      true);
 }
 
 // read-locked like the reference's Len/Dims (graph.go:421,829): a concurrent Add may grow h->layers

@@ -311,6 +311,22 @@ int launch_split_rows(const float* src, int64_t r0, int64_t r1, int pitch, int64
                       hipStream_t s);
 int launch_max_norm(const float* norms, int64_t n, float* out, hipStream_t s);
 
+// ---- filtered exact search: the allowed rows as a dense row set (rowset.hip) ----
+// The ascending ids of the rows whose filter bit is set (filter: fwords bitmap words) and whose
+// `dead` byte (nullable) is clear -> ids[0 .. count), count <= cap; words [ceil(n / 32)], mask
+// [32 ceil(n / 32)] (1 = not allowed) and block_cnt [rowset_blocks(n)] are its workspace.  The
+// order is by ballot ranks and a prefix over blocks: the same list every time.
+int64_t rowset_blocks(int64_t n);
+int launch_rowset_compact(const uint32_t* filter, int64_t fwords, const uint8_t* dead, int64_t n, uint32_t* words,
+                          uint8_t* mask, uint32_t* block_cnt, uint32_t* ids, int64_t cap, hipStream_t s);
+// rows ids[0 .. m) of a K-blocked fp16 plane (ld_src rows per K-block) -> rows 0 .. m of dst
+// (ld_dst rows per K-block), with their unscale and norm
+int launch_rowset_gather(const uint16_t* src, int64_t ld_src, const uint32_t* ids, int64_t m, int pitch, uint16_t* dst,
+                         int64_t ld_dst, const float* xinv, const float* xnorm, float* xinv_out, float* xnorm_out,
+                         hipStream_t s);
+// cand[i] (a position in the row set, or EMPTY_ID) -> ids[cand[i]]
+int launch_rowset_remap(uint32_t* cand, int64_t total, const uint32_t* ids, int64_t m, hipStream_t s);
+
 // certificate of the re-rank (nullable pieces disable it)
 struct CertArgs {
     const float* bound;          // [B] from k_select; nullptr = no certificate

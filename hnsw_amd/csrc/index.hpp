@@ -226,6 +226,17 @@ struct mhnsw_index {
     bool filters_dirty = false;            // the table is to be uploaded
     int filter_route = 1024;               // route width of a filtered search that names none
     DevBuf<int32_t> fof;                   // a host-pointer filtered search's filter_of
+    // filtered exact search (rowset.hip): the allowed rows of the call's filter as a row set --
+    // bitmap words, per-block counts, row mask of the fallback, the ascending ids, their rows
+    // of the fp16 plane and those rows' unscale / norm.  Grow-only, rebuilt by every call.
+    DevBuf<uint32_t> fxwords, fxcnt, fxids;
+    DevBuf<uint8_t> fxmask;
+    DevBuf<uint16_t> fxplane;
+    DevBuf<float> fxinv, fxnorm;
+    // stage marks of the last filtered exact search: start, compaction done, gather done, and
+    // around the first query chunk's re-rank and fallback (options "last_fx_*_ns")
+    hipEvent_t fxev[6] = {};
+    bool have_fx_timing = false;
     std::string err;
     mutable std::shared_mutex mu;
 };
@@ -287,6 +298,7 @@ constexpr int MHNSW_MAX_FILTERS = 1024;
 void drop_filters(mhnsw_index* h);
 int filters_fit(mhnsw_index* h);
 int search_filtered_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int ef, int route, const int32_t* filter_of, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool sticky);
+int search_filtered_exact_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int filter, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool sticky);
 int import_csr(mhnsw_index* h, int64_t N, int dim, int L, int cap, const int64_t* keys, const float* vecs, const int32_t* deg, const int32_t* adj, const int32_t* entry, const uint8_t* dead);
 const char* metric_name(int m);
 int strkey_relabel(mhnsw_index* h);

@@ -5,7 +5,9 @@
 // outputs, error word), walk_args (the walk kernels' SearchArgs, the visited-set rule), finish
 // and read_error / device_error.  The plain search is exact_prepare + exact_run (score GEMM,
 // fused preselection, bucket select, canonical re-rank, certificate, fallback), beam_search
-// or compat_search.  Last, the negative-example re-ranking.
+// or compat_search.  exact_prepare / exact_run work on a RowSet: every row of the index, or
+// (search_filtered_exact) a filter's allowed rows gathered into a dense plane (rowset.hip).
+// Last, the negative-example re-ranking.
 #include "index.hpp"
 
 using namespace mhh;
@@ -252,6 +254,18 @@ static int compat_search(mhnsw_index* h, const SearchCall& c, const SearchArgs& 
     return 0;
 }
 
+// The rows the exact pipeline scores.  The plain search's is the identity: every row of the
+// index, the planes and per-row constants the handle caches, deleted rows masked.  A filtered
+// exact search's is the filter's allowed rows gathered into a dense plane (rowset.hip): n and
+// ld are the host's count of them, exact_run fills the plane, and ids maps a position to its row.
+struct RowSet {
+    int64_t n, ld;        // rows, and rows per K-block of the plane
+    int precision;        // exact_precision the scores run at
+    const uint32_t* ids;  // position -> row id (nullptr: the identity)
+    const uint32_t* filter;  // the allowed rows' bitmap of fwords words (a gathered set)
+    int64_t fwords;
+};
+
 // what exact_prepare decides for exact_run (the names are the two functions' locals)
 struct ExactPlan {
     bool split, h1, h2;
@@ -260,23 +274,54 @@ struct ExactPlan {
     const uint8_t* xdead;
     GraphDev g;
     CertArgs cert;
+    RowSet rs;
+    int fnseg;  // a gathered set's fallback sweeps every row of the index: its segments
+    int64_t fseglen;
 };
 
+// rows the brute force skips: deleted ones, and the live rows of a failed
+// insert that never reached layer 0 (graph.go:1009 leaves them in upper
+// layers only; Search cannot return them)
+static int exact_skipped(mhnsw_index* h, hipStream_t s, const uint8_t*& xdead) {
+    int r;
+    xdead = h->any_dead ? h->dead : nullptr;
+    if (h->partial_rows && h->xgone_epoch != h->mut_epoch) {  // rebuilt only after a mutation
+        // a Delete or a replacement sweep may have killed the last partial rows
+        std::vector<uint8_t> gone((size_t)h->n);
+        int64_t partial = 0;
+        for (int64_t i = 0; i < h->n; ++i) {
+            const bool p = !h->hdead[i] && !in_layer(h, i, 0);
+            partial += p;
+            gone[i] = h->hdead[i] || p;
+        }
+        h->partial_rows = partial;
+        if (partial) {
+            if ((r = ensure_buf(h, h->xgone, (size_t)std::max<int64_t>(h->n, 1)))) return r;
+            HIPCHK(h, hipMemcpyAsync(h->xgone.p, gone.data(), (size_t)h->n, hipMemcpyHostToDevice, s));
+            HIPCHK(h, hipStreamSynchronize(s));
+        }
+        h->xgone_epoch = h->mut_epoch;
+    }
+    if (h->partial_rows) xdead = h->xgone.p;
+    return 0;
+}
+
 // the exact path's workspace, the rows it skips and the certificate constants
-static int exact_prepare(mhnsw_index* h, const SearchCall& c, ExactPlan& plan) {
+static int exact_prepare(mhnsw_index* h, const SearchCall& c, const RowSet& rs, ExactPlan& plan) {
     int r;
     const int k = c.k;
     hipStream_t s = c.s;
     if (k > 256) return fail(h, MHNSW_EUNSUPPORTED, "exact mode supports k <= 256");
-    const bool split = h->exact_precision != 0;
+    const int64_t N = rs.n;  // rows scored
+    const bool split = rs.precision != 0;
     // fp16 1-product with the fused preselection (needs one full sample tile of rows)
-    const bool h1 = h->exact_precision == 3 && h->n >= H1_BN;
-    const bool h2 = h->exact_precision >= 2;  // fp16 row plane (1- and 2-product)
+    const bool h1 = rs.precision == 3 && N >= H1_BN;
+    const bool h2 = rs.precision >= 2;  // fp16 row plane (1- and 2-product)
     // preselect width: the fp16 2-product scores carry a ~2x larger error bound, so the
     // kk-th score must sit further from the k-th distance for the certificate
     const int kk = h->exact_kk > 0 ? std::min(256, std::max(h->exact_kk, k))
                                    : std::min(256, h2 ? std::max(2 * k, 64) : std::max(2 * k, k + 16));
-    const int64_t ldS = (h->n + 255) / 256 * 256;
+    const int64_t ldS = (N + 255) / 256 * 256;
     const int64_t budget = (int64_t)4 << 30;  // score workspace bytes
     int64_t qc = std::max<int64_t>(1, std::min<int64_t>(c.B, budget / (ldS * 4)));
     qc = std::min<int64_t>(qc, 4096);
@@ -294,7 +339,14 @@ static int exact_prepare(mhnsw_index* h, const SearchCall& c, ExactPlan& plan) {
     };
     int nseg;
     int64_t seglen;
-    segs(h->n, nseg, seglen);
+    segs(N, nseg, seglen);
+    int fnseg = nseg;
+    int64_t fseglen = seglen;
+    if (rs.ids) {
+        segs(h->n, fnseg, fseglen);
+        if ((r = ensure_buf(h, h->xsegd, (size_t)qc * fnseg * kk)) || (r = ensure_buf(h, h->xsegi, (size_t)qc * fnseg * kk)))
+            return r;
+    }
     if ((r = ensure_buf(h, h->xsegd, (size_t)qc * nseg * kk)) || (r = ensure_buf(h, h->xsegi, (size_t)qc * nseg * kk)))
         return r;
     // fused preselection (h1): the sample = every stride-th full row tile (about 32
@@ -302,11 +354,11 @@ static int exact_prepare(mhnsw_index* h, const SearchCall& c, ExactPlan& plan) {
     // sample is every tile); a row passes at a rate of ~J / sample rows
     // the GEMM variant this search runs (exact_tile 0: the default, k_h1_pp16; a shape
     // it does not admit runs the ring kernel's filter)
-    const int ev = h1_effective_variant(h->exact_tile, h->pitch, std::max<int64_t>(qc, h->capn));
+    const int ev = h1_effective_variant(h->exact_tile, h->pitch, std::max<int64_t>(qc, rs.ld));
     const int bm = h1_tile_bm(ev);
-    const int64_t nnt = (h->n + H1_BN - 1) / H1_BN, nqt = (qc + bm - 1) / bm;
+    const int64_t nnt = (N + H1_BN - 1) / H1_BN, nqt = (qc + bm - 1) / bm;
     const int stride = (int)std::max<int64_t>(1, std::min<int64_t>(128, (nnt + h->exact_sample - 1) / h->exact_sample));
-    const int64_t nsamp = h1 ? ((h->n / H1_BN) - 1) / stride + 1 : 0;  // sampled full tiles
+    const int64_t nsamp = h1 ? ((N / H1_BN) - 1) / stride + 1 : 0;  // sampled full tiles
     const int J = stride < 8 ? kk : h->exact_thr_rank > 0 ? std::min(kk, std::max(k, h->exact_thr_rank)) : std::max(k, kk / 8);
     // the score workspace: every (query, row) score (precisions 0-2, and their
     // fallback), or only the sample's (fused path: its fallback streams distances
@@ -329,13 +381,13 @@ static int exact_prepare(mhnsw_index* h, const SearchCall& c, ExactPlan& plan) {
                          ? 8 * H1_REC * (int)std::min<int64_t>(512, std::max<int64_t>(64, 4 * bm * J * H1_BN / ns / 8))
                          : (int)std::min<int64_t>((int64_t)bm * H1_BN, std::max<int64_t>(2048, 4 * bm * J * H1_BN / ns) + 7) / 8 * 8;
     const int rsub = h1_region_split(ev);
-    const int scap = (int)std::min<int64_t>(std::max<int64_t>(h->n, 1),
-                                            std::max<int64_t>(512, 8 * J * h->n / ns / H1_BSUB));
+    const int scap = (int)std::min<int64_t>(std::max<int64_t>(N, 1),
+                                            std::max<int64_t>(512, 8 * J * N / ns / H1_BSUB));
     if (h1 && ((r = ensure_buf(h, h->h1thr, (size_t)qc)) || (r = ensure_buf(h, h->h1c, (size_t)nqt * bm + 256)) ||
                (r = ensure_buf(h, h->h1s, (size_t)nqt * bm + 256)) ||
                (r = ensure_buf(h, h->h1region, (size_t)nqt * nnt * rcap)) ||
                (r = ensure_buf(h, h->h1rcnt, (size_t)nqt * nnt * rsub)) ||
-               (r = ensure_buf(h, h->h1xw, (size_t)std::max<int64_t>(h->n, 1) * 4)) ||
+               (r = ensure_buf(h, h->h1xw, (size_t)std::max<int64_t>(N, 1) * 4)) ||
                (r = ensure_buf(h, h->h1qcnt, (size_t)qc * H1_BSUB * H1_CSTRIDE)) || (r = ensure_buf(h, h->h1ovf, (size_t)qc)) ||
                (r = ensure_buf(h, h->h1bucket, (size_t)qc * H1_BSUB * scap)) || (r = ensure_buf(h, h->qerr, 1)) ||
                (r = ensure_buf(h, h->xsegd, (size_t)qc * sseg * J)) ||
@@ -359,28 +411,8 @@ static int exact_prepare(mhnsw_index* h, const SearchCall& c, ExactPlan& plan) {
     if ((r = sync_layer_table(h)) || (r = order_meta(h, s))) return r;
     GraphDev g = graph_view(h);
     g.err = c.errw;
-    // rows the brute force skips: deleted ones, and the live rows of a failed
-    // insert that never reached layer 0 (graph.go:1009 leaves them in upper
-    // layers only; Search cannot return them)
-    const uint8_t* xdead = h->any_dead ? h->dead : nullptr;
-    if (h->partial_rows && h->xgone_epoch != h->mut_epoch) {  // rebuilt only after a mutation
-        // a Delete or a replacement sweep may have killed the last partial rows
-        std::vector<uint8_t> gone((size_t)h->n);
-        int64_t partial = 0;
-        for (int64_t i = 0; i < h->n; ++i) {
-            const bool p = !h->hdead[i] && !in_layer(h, i, 0);
-            partial += p;
-            gone[i] = h->hdead[i] || p;
-        }
-        h->partial_rows = partial;
-        if (partial) {
-            if ((r = ensure_buf(h, h->xgone, (size_t)std::max<int64_t>(h->n, 1)))) return r;
-            HIPCHK(h, hipMemcpyAsync(h->xgone.p, gone.data(), (size_t)h->n, hipMemcpyHostToDevice, s));
-            HIPCHK(h, hipStreamSynchronize(s));
-        }
-        h->xgone_epoch = h->mut_epoch;
-    }
-    if (h->partial_rows) xdead = h->xgone.p;
+    const uint8_t* xdead;
+    if ((r = exact_skipped(h, s, xdead))) return r;
     g.dead = xdead;
     // certificate constants (u = 2^-24; gamma_n = n u / (1 - n u) bounds any
     // order of n-term f32 summation relative to the sum of magnitudes)
@@ -408,17 +440,20 @@ static int exact_prepare(mhnsw_index* h, const SearchCall& c, ExactPlan& plan) {
     cert.xerr = h2 ? h->xerr.p : nullptr;
     cert.qerr = h1 ? h->qerr.p : nullptr;
     plan = ExactPlan{split, h1, h2, kk, nseg, ev, bm, stride, J, sseg, rcap, rsub, scap, ldS, qc, seglen, nnt, nsamp, sseglen,
-                     xdead, g, cert};
+                     xdead, g, cert, rs, fnseg, fseglen};
     return 0;
 }
 
 // the exact path's kernels: per chunk of qc queries the scores, the selection, the re-rank and the fallback
 static int exact_run(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan) {
     const auto& [split, h1, h2, kk, nseg, ev, bm, stride, J, sseg, rcap, rsub, scap, ldS, qc, seglen, nnt, nsamp, sseglen,
-                 xdead, g, cert] = plan;
+                 xdead, g, cert, rs, fnseg, fseglen] = plan;
     const int k = c.k;
     hipStream_t s = c.s;
+    const bool gathered = rs.ids != nullptr;
+    const bool marks = gathered && c.timing;  // the stage marks of a filtered exact search
     if (c.timing) HIPCHK(h, hipEventRecord(h->ev0, s));
+    if (marks) HIPCHK(h, hipEventRecord(h->fxev[0], s));
     if (split && h->xsplit_rows < h->n) {
         uint16_t* xh = h->xsplit.p;
         uint16_t* xl = h->xsplit.p + (size_t)h->capn * h->pitch;
@@ -431,6 +466,26 @@ static int exact_run(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan)
             LCHK(h, launch_split_rows(h->vecs, h->xsplit_rows, h->n, h->pitch, h->capn, xh, xl, s));
         h->xsplit_rows = h->n;
     }
+    // the set's plane, per-row constants and masked rows: the handle's, or the allowed rows'
+    // gathered from them (the measured rounding bound xerr of every row holds for a subset)
+    const uint16_t* Xh = h->xsplit.p;
+    int64_t ldX = h->capn;
+    const float* xinv = h->xinv.p;
+    const float* xnorm = h->norms;
+    const uint8_t* sdead = xdead;
+    if (gathered) {
+        LCHK(h, launch_rowset_compact(rs.filter, rs.fwords, xdead, h->n, h->fxwords.p, h->fxmask.p, h->fxcnt.p,
+                                      h->fxids.p, rs.n, s));
+        if (marks) HIPCHK(h, hipEventRecord(h->fxev[1], s));
+        LCHK(h, launch_rowset_gather(h->xsplit.p, h->capn, rs.ids, rs.n, h->pitch, h->fxplane.p, rs.ld, h->xinv.p,
+                                     h->norms, h->fxinv.p, h->fxnorm.p, s));
+        if (marks) HIPCHK(h, hipEventRecord(h->fxev[2], s));
+        Xh = h->fxplane.p;
+        ldX = rs.ld;
+        xinv = h->fxinv.p;
+        xnorm = h->fxnorm.p;
+        sdead = nullptr;
+    }
     if (h->metric == EUCLIDEAN) {
         HIPCHK(h, hipMemsetAsync(h->xmaxn.p, 0, sizeof(float), s));
         LCHK(h, launch_max_norm(h->norms, h->n, h->xmaxn.p, s));
@@ -439,9 +494,9 @@ static int exact_run(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan)
         const int64_t nb = std::min(qc, c.B - q0);
         ExactArgs a{};
         a.X = h->vecs;
-        a.xnorm = h->norms;
-        a.dead = xdead;
-        a.N = h->n;
+        a.xnorm = xnorm;
+        a.dead = sdead;
+        a.N = rs.n;
         a.Q = h->qpad.p + (size_t)q0 * h->pitch;
         a.qnorm = h->qnorm.p + q0;
         a.B = nb;
@@ -462,14 +517,14 @@ static int exact_run(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan)
         int32_t* on_ = c.dn + q0;
         int32_t* oi_ = c.out_ids ? c.out_ids + q0 * k : nullptr;
         if (split) {
-            a.Xh = h->xsplit.p;
-            a.Xl = h->xsplit.p + (size_t)h->capn * h->pitch;
-            a.ldXs = h->capn;
+            a.Xh = Xh;
+            a.Xl = Xh + (size_t)ldX * h->pitch;  // (bf16x3 only: never a gathered set's)
+            a.ldXs = ldX;
             a.Qh = h->qsplit.p;
             a.Ql = h->qsplit.p + (size_t)qc * h->pitch;
             a.ldQs = qc;
             if (h1) {
-                a.xinv = h->xinv.p;
+                a.xinv = xinv;
                 a.qinv = h->qinv.p;
                 HIPCHK(h, hipMemsetAsync(h->qerr.p, 0, sizeof(float), s));
                 LCHK(h, launch_split_h16(a.Q, 0, nb, h->pitch, qc, h->qsplit.p, nullptr, h->qinv.p, h->qerr.p, s));
@@ -497,7 +552,7 @@ static int exact_run(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan)
                 a.rcap = rcap;
                 a.xw = reinterpret_cast<const float4*>(h->h1xw.p);
                 if (q0 == 0)
-                    LCHK(h, launch_h1_rowconst(h->xinv.p, h->norms, xdead, h->n, h->metric,
+                    LCHK(h, launch_h1_rowconst(xinv, xnorm, sdead, rs.n, h->metric,
                                                reinterpret_cast<float4*>(h->h1xw.p), s));
                 if (c.timing && q0 == 0) HIPCHK(h, hipEventRecord(h->gev0, s));
                 LCHK(h, launch_h1_filter(a, ev, s));
@@ -510,7 +565,7 @@ static int exact_run(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan)
                                       h->h1bucket.p, scap, h->h1ovf.p, rsub, h1_records(ev) ? 1 : 0, a, s));
                 LCHK(h, launch_select_bucket(a, h->h1qcnt.p, h->h1bucket.p, scap, h->h1ovf.p, h->h1thr.p, s));
             } else if (h2) {
-                a.xinv = h->xinv.p;
+                a.xinv = xinv;
                 a.qinv = h->qinv.p;
                 LCHK(h, launch_split_h16(a.Q, 0, nb, h->pitch, qc, h->qsplit.p, h->qsplit.p + (size_t)qc * h->pitch,
                                          h->qinv.p, nullptr, s));
@@ -525,16 +580,29 @@ static int exact_run(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan)
         }
         if (!h1) LCHK(h, launch_exact_select(a, s));
         if (h1 && h1_timing_diag(ev)) continue;  // timing diagnostic: no re-rank, no results
+        if (gathered) LCHK(h, launch_rowset_remap(h->cand.p, nb * kk, rs.ids, rs.n, s));
+        const bool mark0 = marks && q0 == 0;
+        if (mark0) HIPCHK(h, hipEventRecord(h->fxev[3], s));
         HIPCHK(h, hipMemsetAsync(h->xnflag.p, 0, sizeof(int32_t), s));
         CertArgs c1 = cert;
         c1.bound = h->xbound.p;
         c1.qnorm = h->qnorm.p + q0;
         LCHK(h, launch_rerank(a.Q, g, h->cand.p, kk, nb, h->lpr, h->vpl, k, ok_, od_, on_, oi_, c1, s));
+        if (mark0) HIPCHK(h, hipEventRecord(h->fxev[4], s));
         // uncertified queries: canonical distances of every row, then select + re-rank again
         ExactArgs a2 = a;
         a2.only = h->xflag.p;
         a2.bound = nullptr;
-        if (h1) {
+        if (gathered) {
+            // ... of every row of the index the call's mask lets through (the allowed rows: the
+            // same canonical distances as the certified path's), candidates as row ids
+            GraphDev gm = g;
+            gm.dead = h->fxmask.p;
+            a2.N = h->n;
+            a2.nseg = fnseg;
+            a2.seglen = fseglen;
+            LCHK(h, launch_fallback_select(a.Q, gm, a2, h->lpr, h->vpl, s));
+        } else if (h1) {
             LCHK(h, launch_fallback_select(a.Q, g, a2, h->lpr, h->vpl, s));
         } else {
             LCHK(h, launch_exact_fallback(a.Q, g, h->n, h->xflagged.p, h->xnflag.p, h->scores.p, ldS, h->lpr,
@@ -544,9 +612,11 @@ static int exact_run(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan)
         CertArgs c2{};
         c2.only = h->xflag.p;
         LCHK(h, launch_rerank(a.Q, g, h->cand.p, kk, nb, h->lpr, h->vpl, k, ok_, od_, on_, oi_, c2, s));
+        if (mark0) HIPCHK(h, hipEventRecord(h->fxev[5], s));
     }
     if (c.timing) HIPCHK(h, hipEventRecord(h->ev1, s));
-    if (h->exact_precision == 3 && h->n >= H1_BN && h1_timing_diag(ev))
+    h->have_fx_timing = marks;
+    if (h1 && h1_timing_diag(ev))
         return fail(h, MHNSW_EUNSUPPORTED, "exact_tile %d is a timing diagnostic: no results", h->exact_tile);
     return 0;
 }
@@ -570,7 +640,8 @@ static int search_plain(mhnsw_index* h, SearchCall& c, int mode, int ef, const i
     if ((r = stage(h, c))) return r;
     if (mode == MHNSW_MODE_EXACT) {
         ExactPlan plan;
-        if (!(r = exact_prepare(h, c, plan))) r = exact_run(h, c, plan);
+        const RowSet every{h->n, h->capn, h->exact_precision, nullptr, nullptr, 0};
+        if (!(r = exact_prepare(h, c, every, plan))) r = exact_run(h, c, plan);
     } else {
         const bool beam = mode == MHNSW_MODE_BEAM;
         SearchArgs a;
@@ -624,6 +695,70 @@ static int search_filtered(mhnsw_index* h, SearchCall& c, int ef, int route, con
     HIPCHK(h, hipEventRecord(h->ev1, c.s));
     h->have_gemm_timing = false;
     return finish(h, c);
+}
+
+// The filtered exact search of one filter (>= 0): the exact pipeline over the filter's allowed
+// rows as a gathered row set.  The host's mirror of the bitmap sizes the launches (the same
+// words and skipped rows the compaction kernel counts).  Always timed, with stage marks.
+static int search_filtered_exact(mhnsw_index* h, SearchCall& c, int filter) {
+    int r = validate(h);
+    if (r || (r = check_args(h, c, MHNSW_MODE_EXACT))) return r;
+    if (c.k > 256) return fail(h, MHNSW_EUNSUPPORTED, "exact mode supports k <= 256");
+    if (filter < 0 || filter >= (int)h->filters.size() || !h->filters[filter].used)
+        return fail(h, MHNSW_EINVAL, "unknown filter %d", filter);
+    if (c.B <= 0) return 0;
+    h->have_gemm_timing = false;
+    h->have_fx_timing = false;
+    if (!h->layers_exist || live_count(h) == 0) return zero_counts(h, c);
+    // a bitmap that has to grow with the rows moves: nothing enqueued may read it
+    const size_t words = (size_t)((h->capn + 31) / 32);
+    const auto grows = [&](const mhnsw_index::Filter& F) { return F.used && F.bits.size() < words; };
+    if (std::any_of(h->filters.begin(), h->filters.end(), grows) && (r = drain(h))) return r;
+    if ((r = filters_fit(h))) return r;
+    const uint8_t* xdead;
+    if ((r = exact_skipped(h, c.s, xdead))) return r;
+    const mhnsw_index::Filter& F = h->filters[filter];
+    const int64_t nwords = (h->n + 31) / 32, fwords = std::min<int64_t>(nwords, (int64_t)F.bits.size());
+    int64_t m = 0;
+    for (int64_t w = 0; w < fwords; ++w) {
+        uint32_t bits = F.bits[(size_t)w];
+        if (w == nwords - 1 && (h->n & 31)) bits &= (1u << (h->n & 31)) - 1u;
+        if (!h->any_dead && !h->partial_rows) {
+            m += __builtin_popcount(bits);
+            continue;
+        }
+        for (; bits; bits &= bits - 1) {
+            const int64_t i = w * 32 + __builtin_ctz(bits);
+            m += !h->hdead[(size_t)i] && (!h->partial_rows || in_layer(h, i, 0));
+        }
+    }
+    if (m == 0) {  // nothing allowed: no row, no error
+        h->stats_host[6] += c.B;
+        h->have_timing = false;
+        return zero_counts(h, c);
+    }
+    // without an fp16 row plane (exact_precision 0 or 1) the call scores at precision 3
+    const RowSet rs{m, (m + 255) / 256 * 256, h->exact_precision >= 2 ? h->exact_precision : 3, nullptr, F.d, fwords};
+    if ((r = ensure_buf(h, h->fxwords, (size_t)nwords)) || (r = ensure_buf(h, h->fxmask, (size_t)nwords * 32)) ||
+        (r = ensure_buf(h, h->fxcnt, (size_t)rowset_blocks(h->n))) || (r = ensure_buf(h, h->fxids, (size_t)m)) ||
+        (r = ensure_buf(h, h->fxplane, (size_t)rs.ld * h->pitch)) || (r = ensure_buf(h, h->fxinv, (size_t)rs.ld)) ||
+        (r = ensure_buf(h, h->fxnorm, (size_t)rs.ld)))
+        return r;
+    RowSet rset = rs;
+    rset.ids = h->fxids.p;
+    if ((r = stage(h, c))) return r;
+    ExactPlan plan;
+    if (!(r = exact_prepare(h, c, rset, plan))) r = exact_run(h, c, plan);
+    return r ? r : finish(h, c);
+}
+
+int search_filtered_exact_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int filter,
+                               int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool sticky) {
+    // filter -1 (every live row) is the plain exact search
+    if (filter == -1) return search_impl(h, queries, on_device, B, dim, k, MHNSW_MODE_EXACT, 0, nullptr, okeys, odist, on, s,
+                                         true, nullptr, sticky);
+    SearchCall c{queries, on_device, B, dim, k, okeys, odist, on, nullptr, s, sticky, true};
+    return on_scratch(h, s, [&] { return search_filtered_exact(h, c, filter); });
 }
 
 int search_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int mode, int ef,

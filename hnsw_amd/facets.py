@@ -2,7 +2,7 @@
 search.go) over this engine.
 
 A FacetedGraph pairs a Graph with a store of per-key attributes.  Its Search
-has two modes:
+has three modes:
 
 MODE_COMPAT  the reference's procedure, literally (search.go:15-88): Search for
              k * expandFactor neighbours, keep the ones whose facets match, ask
@@ -12,6 +12,9 @@ MODE_BEAM    the engine's filtered beam search (Graph.search_filtered_arrays):
              the keys of store.Filter(filters) become a device-resident
              allow-list (cached per filter list) and the predicate is applied
              inside the layer-0 walk; expandFactor does not apply.
+MODE_EXACT   the same allow-list, searched by the engine's filtered exact
+             search (brute force over the allowed rows only): the exact k
+             nearest matching nodes; expandFactor, ef and route do not apply.
 
 Go's interface{} values are Python objects here.  reflect.DeepEqual is typed:
 an int never equals a float, so values compare equal only within one type.
@@ -26,7 +29,7 @@ import numpy as np
 from ._lib import HnswError
 from .graph import Graph, Node
 
-MODE_COMPAT, MODE_BEAM = 0, 1
+MODE_COMPAT, MODE_BEAM, MODE_EXACT = 0, 1, 2
 
 
 class FacetError(Exception):  # facets.go:279-286
@@ -269,19 +272,19 @@ class FacetedGraph:  # search.go:166-329
             raise FacetError("k must be greater than 0")
         if mode == MODE_COMPAT:
             return self._search_compat(query, filters, k, expandFactor)
-        if mode != MODE_BEAM:
+        if mode not in (MODE_BEAM, MODE_EXACT):
             raise FacetError(f"unknown search mode {mode}")
         q = np.asarray(query, np.float32).reshape(1, -1)
         f, cached = self._device_filter(filters)
         try:
             try:
-                keys, _, n = self.Graph.search_filtered_arrays(q, k, f, ef=ef, route=route)
+                keys, _, n = self.Graph.search_filtered_arrays(q, k, f, ef=ef, route=route, mode=mode)
             except HnswError as e:
                 if not cached or "unknown filter" not in str(e):
                     raise
                 # the graph was Imported since: its filters are gone, the store's keys are not
                 f, cached = self._device_filter(filters, fresh=True)
-                keys, _, n = self.Graph.search_filtered_arrays(q, k, f, ef=ef, route=route)
+                keys, _, n = self.Graph.search_filtered_arrays(q, k, f, ef=ef, route=route, mode=mode)
         finally:
             if not cached:
                 f.close()

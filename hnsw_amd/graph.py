@@ -547,16 +547,26 @@ class Graph:
                 raise HnswError(-1, "filter of another graph")
         return np.asarray([-1 if f is None else f._fid() for f in filters], np.int32)
 
-    def search_filtered_arrays(self, queries, k: int, filters, ef: int = 0, route: int = 0):
-        """Beam search among the allowed rows -> (keys int64[B,k], dist
+    def search_filtered_arrays(self, queries, k: int, filters, ef: int = 0, route: int = 0, mode: int = MODE_BEAM):
+        """Search among the allowed rows -> (keys int64[B,k], dist
         float32[B,k], n int32[B]).  filters: one Filter, or one per query (None:
-        every live row).  The search routes through a list of `route` entries
+        every live row).  MODE_BEAM routes through a list of `route` entries
         (0: option filter_route) and keeps the max(ef, k) <= 128 best allowed
-        rows; a route too narrow for the filter returns fewer than k."""
+        rows; a route too narrow for the filter returns fewer than k.
+        MODE_EXACT is the brute force over the allowed rows only (one pass per
+        distinct filter; ef and route are ignored): the exact k nearest, which
+        pays at selective filters (DESIGN.md "Filtered exact search")."""
+        if mode not in (MODE_BEAM, MODE_EXACT):
+            raise HnswError(-1, f"filtered search supports MODE_BEAM and MODE_EXACT, got mode {mode}")
         self._sync()
         q, ok, od, on = self._search_io(queries, k)
         B, d = q.shape
         fo = np.ascontiguousarray(self._filter_ids(filters, B))
+        if mode == MODE_EXACT:
+            self._check(load().mhnsw_search_filtered_exact(self._h, _ptr(q, C.c_float), B, d, int(k),
+                                                           _ptr(fo, C.c_int32), _ptr(ok, C.c_int64),
+                                                           _ptr(od, C.c_float), _ptr(on, C.c_int32)))
+            return ok, od, on
         self._check(load().mhnsw_search_filtered(self._h, _ptr(q, C.c_float), B, d, int(k), int(ef), int(route),
                                                  _ptr(fo, C.c_int32), _ptr(ok, C.c_int64), _ptr(od, C.c_float),
                                                  _ptr(on, C.c_int32)))
@@ -570,9 +580,18 @@ class Graph:
                                                         C.c_void_p(filter_of_ptr), C.c_void_p(keys_ptr),
                                                         C.c_void_p(dist_ptr), C.c_void_p(n_ptr), C.c_void_p(stream)))
 
-    def SearchFiltered(self, near, k: int, filter, ef: int = 0, route: int = 0) -> List[Node]:
+    def search_filtered_exact_device(self, q_ptr: int, B: int, dim: int, k: int, filter, keys_ptr: int,
+                                     dist_ptr: int, n_ptr: int, stream: int = 0):
+        """The MODE_EXACT filtered search on device buffers: one Filter (None:
+        every live row) for the whole batch, enqueued on `stream` (no host sync)."""
+        fid = int(self._filter_ids(filter, 1)[0])
+        self._check(load().mhnsw_search_filtered_exact_device(self._h, C.c_void_p(q_ptr), B, dim, k, fid,
+                                                              C.c_void_p(keys_ptr), C.c_void_p(dist_ptr),
+                                                              C.c_void_p(n_ptr), C.c_void_p(stream)))
+
+    def SearchFiltered(self, near, k: int, filter, ef: int = 0, route: int = 0, mode: int = MODE_BEAM) -> List[Node]:
         q = np.asarray(near, np.float32).reshape(1, -1)
-        ok, _, on = self.search_filtered_arrays(q, k, filter, ef=ef, route=route)
+        ok, _, on = self.search_filtered_arrays(q, k, filter, ef=ef, route=route, mode=mode)
         return self._nodes(ok[0, : on[0]])
 
     def _node(self, key) -> Node:

@@ -393,6 +393,19 @@ class Graph {  // graph.go:305-332
     // EfSearch, route <= 0: the option filter_route
     std::pair<std::vector<Node<K>>, Error> SearchFiltered(const Vector& near, int k, const Filter* filter, int ef = 0,
                                                           int route = 0) {
+        return search_filtered(near, k, filter, ef, route, false);
+    }
+
+    // the exact k nearest rows of `filter` (nullptr: every live row): the brute
+    // force over the allowed rows only (mhnsw_search_filtered_exact), in every
+    // build mode; it pays at selective filters
+    std::pair<std::vector<Node<K>>, Error> SearchFilteredExact(const Vector& near, int k, const Filter* filter) {
+        return search_filtered(near, k, filter, 0, 0, true);
+    }
+
+   private:
+    std::pair<std::vector<Node<K>>, Error> search_filtered(const Vector& near, int k, const Filter* filter, int ef,
+                                                           int route, bool exact) {
         sync();
         const int have = Dims();
         if (have && (int)near.size() != have)
@@ -406,14 +419,18 @@ class Graph {  // graph.go:305-332
         if (filter && filter->Owner() != this) return {{}, Error{"filter of another graph", MHNSW_EINVAL}};
         if (filter && filter->Id() < 0) return {{}, Error{"unknown filter -1", MHNSW_EINVAL}};  // closed, or never made
         const int32_t fo = filter ? filter->Id() : -1;
-        const int rc = mhnsw_search_filtered(h_, near.data(), 1, (int)near.size(), k, ef, route, &fo, keys.data(),
-                                             dist.data(), &n);
+        const int rc = exact ? mhnsw_search_filtered_exact(h_, near.data(), 1, (int)near.size(), k, &fo, keys.data(),
+                                                           dist.data(), &n)
+                             : mhnsw_search_filtered(h_, near.data(), 1, (int)near.size(), k, ef, route, &fo,
+                                                     keys.data(), dist.data(), &n);
         if (rc < 0) return {{}, make_error(rc, h_)};
         std::vector<Node<K>> out;
         const std::vector<K> ks = Codec::decode(h_, keys.data(), (size_t)n);
         for (const K& key : ks) out.push_back(Node<K>{key, lookup_value(key)});
         return {out, {}};
     }
+
+   public:
 
     int Len() const { return (int)mhnsw_len(h_); }   // graph.go:829
     int Dims() const { return mhnsw_dims(h_); }      // graph.go:421

@@ -11,7 +11,19 @@ lists filtered afterwards (here on the device; a caller would copy B x W results
 to the host first), its kernel ms and its recall after filtering.
 
 Writes <out>/filtered_search.txt and .json.
-Usage: python tools/filter_probe.py [--out profiles]"""
+
+--leg exact: the filtered exact search (mhnsw_search_filtered_exact_device) on the
+same index, batches and k, random filters of 100 / 50 / 10 / 1 / 0.1 % of the rows.
+Per selectivity, warmed and alternating in one session: the exact call's kernel ms
+(compaction through re-rank) with its stage split (compaction, gather, and of the
+first query chunk scores + selection, re-rank, fallback), its uncertified queries
+and its recall@10 against the masked fp32 brute force; the filtered walk at the
+route the walk's table uses for that selectivity (256 / 256 / 1024 / 2048 / 2048)
+with its recall and its queries below k; and the unfiltered MODE_EXACT search, the
+ceiling of the 100 % case.  --bench-lines FILE: lines copied into the write-up (the
+parent's and this tree's bench.py result lines).  Writes <out>/filtered_exact.txt and
+.json.
+Usage: python tools/filter_probe.py [--leg walk|exact] [--out profiles]"""
 import argparse
 import json
 import os
@@ -28,6 +40,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles"))
 ap.add_argument("--nbase", type=int, default=1_000_000)
 ap.add_argument("--batch", type=int, default=16384)
+ap.add_argument("--leg", choices=["walk", "exact"], default="walk")
+ap.add_argument("--bench-lines", default=None)
 args = ap.parse_args()
 
 dev = torch.device("cuda")
@@ -78,6 +92,86 @@ def filtered(fo, W):
     torch.cuda.synchronize()
     return g.last_kernel_ms()
 
+
+def exact_leg():
+    rows, lines = [], []
+    rng = np.random.default_rng(99)
+    plain = Searcher(g, B, K, d, dev)
+    stages = ("compact", "gather", "select", "rerank", "fallback")
+
+    def unfiltered():
+        plain.run(Q, H.MODE_EXACT, 0)
+        torch.cuda.synchronize()
+        return g.last_kernel_ms()
+
+    for pct, W in ((100, 256), (50, 256), (10, 1024), (1, 2048), (0.1, 2048)):
+        allowed_h = np.ones(n, bool) if pct == 100 else rng.random(n) < pct / 100.0
+        allowed = torch.tensor(allowed_h, device=dev)
+        f = g.Filter(np.flatnonzero(allowed_h))
+        fo = torch.full((B,), f.id, dtype=torch.int32, device=dev)
+        truth = masked_truth(allowed)
+
+        def exact():
+            g.search_filtered_exact_device(Q.data_ptr(), B, d, K, f, ok.data_ptr(), od.data_ptr(), on.data_ptr(),
+                                           stream=stream)
+            torch.cuda.synchronize()
+            return g.last_kernel_ms(), [g.get_option(f"last_fx_{s}_ns") / 1e6 for s in stages]
+
+        exact(), filtered(fo, W), unfiltered()
+        e_ms, e_st, w_ms, u_ms = [], [], [], []
+        for _ in range(REPS):
+            ms, st = exact()
+            e_ms.append(ms)
+            e_st.append(st)
+            w_ms.append(filtered(fo, W))
+            u_ms.append(unfiltered())
+        g.device_status()
+        w_keys = torch.where(torch.arange(K, device=dev)[None, :] < on[:, None], ok, torch.full_like(ok, -1))
+        w_recall, w_below = recall(w_keys, truth), int((on.cpu().numpy() < K).sum())
+        g.reset_stats()
+        exact()
+        g.device_status()
+        uncert = g.stats()["exact_uncertified"]
+        e_keys = torch.where(torch.arange(K, device=dev)[None, :] < on[:, None], ok, torch.full_like(ok, -1))
+        st = np.median(np.asarray(e_st), axis=0)
+        med = float(np.median(e_ms))
+        row = {"allowed_pct": pct, "allowed_rows": int(allowed_h.sum()), "exact_kernel_ms": [round(x, 3) for x in e_ms],
+               "exact_kernel_ms_median": round(med, 3),
+               "compaction_ms": round(float(st[0]), 3), "gather_ms": round(float(st[1]), 3),
+               "pipeline_ms": round(med - float(st[0]) - float(st[1]), 3),
+               "first_chunk_scores_selection_ms": round(float(st[2]), 3), "first_chunk_rerank_ms": round(float(st[3]), 3),
+               "first_chunk_fallback_ms": round(float(st[4]), 3), "uncertified_queries": int(uncert),
+               "exact_recall_at_10": round(recall(e_keys, truth), 4), "exact_queries_below_k": int((on.cpu().numpy() < K).sum()),
+               "walk_route": W, "walk_kernel_ms": [round(x, 3) for x in w_ms],
+               "walk_kernel_ms_median": round(float(np.median(w_ms)), 3), "walk_recall_at_10": round(w_recall, 4),
+               "walk_queries_below_k": w_below, "unfiltered_exact_kernel_ms": [round(x, 3) for x in u_ms],
+               "unfiltered_exact_kernel_ms_median": round(float(np.median(u_ms)), 3)}
+        rows.append(row)
+        lines.append(f"allowed {pct:5} % ({row['allowed_rows']:7d} rows): exact {row['exact_kernel_ms_median']:8.3f} ms/batch "
+                     f"= compaction {row['compaction_ms']:.3f} + gather {row['gather_ms']:.3f} + pipeline "
+                     f"{row['pipeline_ms']:.3f} (first chunk: scores + selection {row['first_chunk_scores_selection_ms']:.3f}, "
+                     f"re-rank {row['first_chunk_rerank_ms']:.3f}, fallback {row['first_chunk_fallback_ms']:.3f}), "
+                     f"{uncert} uncertified, recall@10 {row['exact_recall_at_10']:.4f} | walk route {W}: "
+                     f"{row['walk_kernel_ms_median']:8.3f} ms/batch, recall@10 {w_recall:.4f}, {w_below} below k | "
+                     f"unfiltered exact {row['unfiltered_exact_kernel_ms_median']:8.3f} ms/batch")
+        print(lines[-1], flush=True)
+        f.close()
+    os.makedirs(args.out, exist_ok=True)
+    head = (f"filtered exact search, bench index {n} x {d} cosine, batches of {B}, k {K}; kernel ms are last_kernel_ms "
+            f"medians of {REPS} repeats after one warm-up, the exact call, the filtered walk (ef {EF}) and the unfiltered "
+            f"exact search alternating; stage times from HIP events (options last_fx_*_ns); recall over the first {NGT} "
+            f"queries against a masked fp32 brute force")
+    bench = open(args.bench_lines).read().splitlines() if args.bench_lines else []
+    with open(os.path.join(args.out, "filtered_exact.txt"), "w") as fh:
+        fh.write(head + "\n" + "\n".join(lines + bench) + "\n")
+    with open(os.path.join(args.out, "filtered_exact.json"), "w") as fh:
+        json.dump({"what": head, "rows": rows, "bench_lines": bench}, fh, indent=1)
+
+
+if args.leg == "exact":
+    exact_leg()
+    g.close()
+    sys.exit(0)
 
 rows, lines = [], []
 rng = np.random.default_rng(99)
