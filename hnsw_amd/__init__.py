@@ -9,7 +9,7 @@ from ._lib import (BUILD_BATCH, BUILD_COMPAT, BUILD_FLAT, COSINE, EUCLIDEAN, KEY
                    KEY_UINT64, MODE_BEAM, MODE_COMPAT, MODE_EXACT, HnswError, LIB_PATH, SIGNATURES, load)
 from .graph import (DOG_QUERY_HACK, CosineDistance, DistanceFunc, EuclideanDistance, Filter, Graph, LoadSavedGraph, MakeNode,
                     NewGraph, NewGraphWithConfig, Node, RegisterDistanceFunc, SavedGraph, SplitMix64Rand, Vector,
-                    distance_func_to_name, max_level, merge_topk_device, random_level, sweep_device)
+                    distance_func_to_name, max_level, merge_topk_device, random_level, split_ragged, sweep_device)
 from .adapters import ExactAdapter, ExactIndex, HNSWAdapter
 
 __all__ = [
@@ -18,4 +18,5 @@ __all__ = [
     "NewGraph", "NewGraphWithConfig", "Node", "RegisterDistanceFunc", "Vector", "distance_func_to_name",
     "merge_topk_device", "KEY_INT", "KEY_INT32", "KEY_INT64", "KEY_UINT32", "KEY_UINT64", "LoadSavedGraph",
     "SavedGraph", "sweep_device", "DOG_QUERY_HACK", "SplitMix64Rand", "max_level", "random_level",
+    "split_ragged",
 ]

@@ -1168,6 +1168,19 @@ void mhnsw_destroy(mhnsw_index* h) {
     F(h->fxplane.p);
     F(h->fxinv.p);
     F(h->fxnorm.p);
+    F(h->rthr.p);
+    F(h->rrad.p);
+    F(h->rdist.p);
+    F(h->rstate.p);
+    F(h->rsweep.p);
+    F(h->rtmp.p);
+    F(h->rcnt.p);
+    F(h->rcursor.p);
+    F(h->rseg.p);
+    F(h->rhits.p);
+    F(h->rstat.p);
+    F(h->rlims.p);
+    F(h->rkeys.p);
     for (auto e : h->fxev)
         if (e) (void)hipEventDestroy(e);
     if (h->scr_ev) (void)hipEventDestroy(h->scr_ev);
@@ -1279,6 +1292,12 @@ int mhnsw_set_option(mhnsw_index* h, const char* name, int64_t v) {
     } else if (n == "exact_sample") {
         if (v < 1 || v > 1 << 20) return fail(h, MHNSW_EINVAL, "exact_sample must be in [1, 2^20]");
         h->exact_sample = (int)v;
+    } else if (n == "range_expect") {
+        if (v < 1 || v > 1 << 20) return fail(h, MHNSW_EINVAL, "range_expect must be in [1, 2^20]");
+        h->range_expect = v;
+    } else if (n == "range_force_fallback") {
+        if (v < 0 || v > 1) return fail(h, MHNSW_EINVAL, "range_force_fallback must be 0 or 1");
+        h->range_force_fallback = (int)v;
     } else if (n == "exact_kk") {
         h->exact_kk = (int)v;
     } else if (n == "exact_tile") {
@@ -1407,6 +1426,31 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
         float ms = 0.f;
         if (i == 5 || !h->have_fx_timing || hipEventSynchronize(h->fxev[i + 1]) != hipSuccess ||
             hipEventElapsedTime(&ms, h->fxev[i], h->fxev[i + 1]) != hipSuccess)
+            return MHNSW_EINVAL;
+        *v = (int64_t)std::llround((double)ms * 1e6);
+    }
+    else if (n == "range_expect") *v = h->range_expect;
+    else if (n == "range_force_fallback") *v = h->range_force_fallback;
+    else if (n == "last_range_candidates" || n == "last_range_fallback_queries") {
+        // read-only: the last range search's counters (waits for it)
+        unsigned long long st[2] = {0, 0};
+        if (!h->have_range_stats) return MHNSW_EINVAL;
+        if ((h->scr_valid && hipEventSynchronize(h->scr_ev) != hipSuccess) ||
+            hipMemcpy(st, h->rstat.p, sizeof st, hipMemcpyDeviceToHost) != hipSuccess)
+            return MHNSW_EDEVICE;
+        *v = (int64_t)st[n == "last_range_candidates" ? 0 : 1];
+    }
+    else if (n.rfind("last_range_", 0) == 0) {
+        // read-only: the last exact-mode range search's stages (HIP events): of its first chunk of
+        // queries the filter (threshold, GEMM, buckets), the refine and the sweep (count, prefix,
+        // gather, write); of the whole call the order stage (sort + emit)
+        static const char* const stage[4] = {"filter", "refine", "sweep", "order"};
+        static const int first[4] = {0, 1, 2, 4};
+        int i = 0;
+        while (i < 4 && n != std::string("last_range_") + stage[i] + "_ns") ++i;
+        float ms = 0.f;
+        if (i == 4 || !h->have_range_timing || hipEventSynchronize(h->fxev[first[i] + 1]) != hipSuccess ||
+            hipEventElapsedTime(&ms, h->fxev[first[i]], h->fxev[first[i] + 1]) != hipSuccess)
             return MHNSW_EINVAL;
         *v = (int64_t)std::llround((double)ms * 1e6);
     }
@@ -1617,6 +1661,32 @@ int mhnsw_search_filtered_exact_device(mhnsw_index* h, const float* d_queries, i
     std::unique_lock<std::shared_mutex> lk(h->mu);
     return search_filtered_exact_impl(h, d_queries, true, B, dim, k, filter, d_keys, d_dist, d_n, (hipStream_t)stream,
                                       true);
+}
+
+int mhnsw_range_search(mhnsw_index* h, const float* queries, int64_t B, int dim, const float* radius, int mode, int ef,
+                       int64_t* out_lims) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    return range_search_impl(h, queries, B, dim, radius, mode, ef, out_lims);
+}
+
+int mhnsw_range_results(mhnsw_index* h, int64_t* out_keys, float* out_dist, int64_t cap) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    const int64_t n = h->range_total;
+    if (n < 0) return fail(h, MHNSW_EINVAL, "no range search results to copy");
+    if (cap < n) return fail(h, MHNSW_EINVAL, "cap %lld is below the %lld hits of the last range search", (long long)cap, (long long)n);
+    if (n == 0) return MHNSW_OK;
+    if (!out_keys || !out_dist) return fail(h, MHNSW_EINVAL, "out_keys and out_dist must be non-NULL");
+    HIPCHK(h, hipMemcpyAsync(out_keys, h->rkeys.p, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out_dist, h->rdist.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MHNSW_OK;
+}
+
+int mhnsw_range_search_device(mhnsw_index* h, const float* d_queries, int64_t B, int dim, const float* d_radius, int mode,
+                              int ef, int64_t cap, int64_t* d_lims, int64_t* d_keys, float* d_dist, void* stream) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    return range_search_device_impl(h, d_queries, B, dim, d_radius, mode, ef, cap, d_lims, d_keys, d_dist,
+                                    (hipStream_t)stream);
 }
 
 // read-locked like the reference's Len/Dims (graph.go:421,829): a concurrent Add may grow h->layers

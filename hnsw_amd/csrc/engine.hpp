@@ -356,4 +356,40 @@ int launch_fallback_select(const float* Q, const GraphDev& g, const ExactArgs& a
 int launch_merge_topk(const int64_t* keys_in, const float* dist_in, const int32_t* n_in, int shards, int64_t B,
                       int k, int64_t* out_keys, float* out_dist, int32_t* out_n, hipStream_t s);
 
+// ---- range search (range.hip): every row within a per-query radius ----
+// One chunk of queries (exact_run's chunking); lims / hits / stat belong to the whole call.
+struct RangeArgs {
+    GraphDev g;
+    const float* Q;        // [B * pitch] the chunk's padded queries
+    const float* radius;   // [B]
+    int64_t B;
+    int32_t* qcnt;         // the filter's sub-bucket counters (launch_bucket); slot 1 of each: the hits refine kept
+    uint2* bucket;         // sub-buckets: candidates in, {row, distance bits} of the hits out (in place)
+    int scap;
+    const uint8_t* qovf;   // [B] a region of the query overflowed
+    uint8_t* state;        // [B] 0: the filter covers the query, 1: sweep, 2: no hit possible (k_range_thr)
+    uint8_t* sweep;        // [B] the sweep answers the query (state 1, or an overflow seen by refine)
+    int32_t* cnt;          // [B] hits
+    int32_t* cursor;       // [B] the sweep's write cursors
+    int64_t* lims;         // [B + 1] the chunk's part of the call's prefix (lims[0]: the chunk's base)
+    unsigned long long* hits;  // [hcap] {order image of the distance, row id}
+    int64_t hcap, cap;     // hit buffer entries; the caller's capacity (queries starting at or past it write nothing)
+    unsigned long long* stat;  // [0] pairs that reached refine, [1] queries the sweep answered
+};
+int launch_range_thr(const RangeArgs& a, const float* qnorm, const float* qinv, const CertArgs& c, int fused, float* thr,
+                     hipStream_t s);
+int launch_range_refine(const RangeArgs& a, int lpr, int vpl, hipStream_t s);
+int launch_range_gather(const RangeArgs& a, hipStream_t s);
+// canonical sweep of rows [0, N) for the queries a.sweep flags: write = false counts, true writes
+int launch_range_sweep(const RangeArgs& a, int64_t N, int nseg, int64_t seglen, bool write, int lpr, int vpl,
+                       hipStream_t s);
+int launch_range_scan(const int32_t* cnt, int64_t B, int64_t* lims, int32_t* cursor, hipStream_t s);
+int range_sort_temp_bytes(int64_t hcap, int64_t B, size_t* bytes);
+int launch_range_order_emit(const unsigned long long* hits, unsigned long long* sorted, int64_t hcap,
+                            const int64_t* lims, int64_t B, int64_t cap, uint32_t* seg_b, uint32_t* seg_e, void* temp,
+                            size_t temp_bytes, const GraphDev& g, int64_t* keys, float* dist, hipStream_t s);
+// beam mode: the beam lists bk / bd / bn [B * ef] cut by the radius -> lims, keys, dist
+int launch_range_beam(const int64_t* bk, const float* bd, const int32_t* bn, int ef, const float* radius, int64_t B,
+                      int32_t* cnt, int64_t* lims, int64_t cap, int64_t* keys, float* dist, hipStream_t s);
+
 }  // namespace mh

@@ -237,6 +237,20 @@ struct mhnsw_index {
     // around the first query chunk's re-rank and fallback (options "last_fx_*_ns")
     hipEvent_t fxev[6] = {};
     bool have_fx_timing = false;
+    // range search (range.hip): per-chunk thresholds, query states and counts, the call's hit
+    // buffer (unsorted and sorted halves), sort segments and temporary storage, the counters of
+    // the last call, and a host-pointer call's radii, prefix and results (mhnsw_range_results)
+    int64_t range_expect = 64;     // expected hits per query: sizes the filter's regions and sub-buckets
+    int range_force_fallback = 0;  // test option: every query takes the canonical sweep
+    DevBuf<float> rthr, rrad, rdist;
+    DevBuf<uint8_t> rstate, rsweep, rtmp;
+    DevBuf<int32_t> rcnt, rcursor;
+    DevBuf<uint32_t> rseg;
+    DevBuf<unsigned long long> rhits, rstat;
+    DevBuf<int64_t> rlims, rkeys;
+    int64_t range_total = -1;  // hits the last host-pointer range search left in rkeys / rdist (-1: none)
+    bool have_range_stats = false;
+    bool have_range_timing = false;  // fxev holds an exact-mode range search's stage marks (options "last_range_*_ns")
     std::string err;
     mutable std::shared_mutex mu;
 };
@@ -299,6 +313,8 @@ void drop_filters(mhnsw_index* h);
 int filters_fit(mhnsw_index* h);
 int search_filtered_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int ef, int route, const int32_t* filter_of, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool sticky);
 int search_filtered_exact_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int filter, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool sticky);
+int range_search_impl(mhnsw_index* h, const float* queries, int64_t B, int dim, const float* radius, int mode, int ef, int64_t* out_lims);
+int range_search_device_impl(mhnsw_index* h, const float* d_queries, int64_t B, int dim, const float* d_radius, int mode, int ef, int64_t cap, int64_t* d_lims, int64_t* d_keys, float* d_dist, hipStream_t s);
 int import_csr(mhnsw_index* h, int64_t N, int dim, int L, int cap, const int64_t* keys, const float* vecs, const int32_t* deg, const int32_t* adj, const int32_t* entry, const uint8_t* dead);
 const char* metric_name(int m);
 int strkey_relabel(mhnsw_index* h);

@@ -307,7 +307,9 @@ static int exact_skipped(mhnsw_index* h, hipStream_t s, const uint8_t*& xdead) {
 }
 
 // the exact path's workspace, the rows it skips and the certificate constants
-static int exact_prepare(mhnsw_index* h, const SearchCall& c, const RowSet& rs, ExactPlan& plan) {
+// (expect > 0, a range search: the regions and sub-buckets are sized for that many passing
+// rows per query over the whole index instead of J over the sample)
+static int exact_prepare(mhnsw_index* h, const SearchCall& c, const RowSet& rs, ExactPlan& plan, int64_t expect = 0) {
     int r;
     const int k = c.k;
     hipStream_t s = c.s;
@@ -373,16 +375,19 @@ static int exact_prepare(mhnsw_index* h, const SearchCall& c, const RowSet& rs, 
     }
     // pairs per tile region / per query sub-bucket: 4x what the threshold lets
     // through on average (~J N / ns per query, ~bm J BN / ns per tile), with floors
-    const int64_t ns = std::max<int64_t>(1, nsamp * H1_BN);
+    const int64_t ns = expect > 0 ? std::max<int64_t>(N, 1) : std::max<int64_t>(1, nsamp * H1_BN);
+    const int64_t Jc = expect > 0 ? expect : J;
     // (a multiple of 8: k_h1_pp16 splits each tile's region among its 8 waves)
     // record-mode variants: per wave 4x the expected records (<= one per passing pair,
     // at most 8 block rows x 64 lanes), H1_REC uint2 each
     const int rcap = h1_records(ev)
-                         ? 8 * H1_REC * (int)std::min<int64_t>(512, std::max<int64_t>(64, 4 * bm * J * H1_BN / ns / 8))
-                         : (int)std::min<int64_t>((int64_t)bm * H1_BN, std::max<int64_t>(2048, 4 * bm * J * H1_BN / ns) + 7) / 8 * 8;
+                         ? 8 * H1_REC * (int)std::min<int64_t>(512, std::max<int64_t>(64, 4 * bm * Jc * H1_BN / ns / 8))
+                         : (int)std::min<int64_t>((int64_t)bm * H1_BN, std::max<int64_t>(2048, 4 * bm * Jc * H1_BN / ns) + 7) / 8 * 8;
     const int rsub = h1_region_split(ev);
+    // (a range search: 8x the expected hits, at least 128 per sub-bucket -- a query that passes
+    // more is answered by the sweep, so the floor only has to cover what the radius lets through)
     const int scap = (int)std::min<int64_t>(std::max<int64_t>(N, 1),
-                                            std::max<int64_t>(512, 8 * J * N / ns / H1_BSUB));
+                                            std::max<int64_t>(expect > 0 ? 128 : 512, 8 * Jc * N / ns / H1_BSUB));
     if (h1 && ((r = ensure_buf(h, h->h1thr, (size_t)qc)) || (r = ensure_buf(h, h->h1c, (size_t)nqt * bm + 256)) ||
                (r = ensure_buf(h, h->h1s, (size_t)nqt * bm + 256)) ||
                (r = ensure_buf(h, h->h1region, (size_t)nqt * nnt * rcap)) ||
@@ -773,6 +778,250 @@ int search_filtered_impl(mhnsw_index* h, const float* queries, bool on_device, i
                          bool sticky) {
     SearchCall c{queries, on_device, B, dim, k, okeys, odist, on, nullptr, s, sticky, true};
     return on_scratch(h, s, [&] { return search_filtered(h, c, ef, route, filter_of); });
+}
+
+// ---- range search: every row within a per-query radius (range.hip; DESIGN.md "Range search") ----
+// Where a range search's ragged result goes, all on the device: lims [B + 1], keys / dist [cap].
+struct RangeOut {
+    const float* radius;  // [B]
+    int64_t cap;
+    int64_t* lims;
+    int64_t* keys;
+    float* dist;
+};
+
+// Exact mode.  Per chunk of queries: the radius as the filter GEMM's threshold, the filter and
+// the buckets as exact_run runs them, the canonical refine of the candidates, the sweep for the
+// queries the filter does not cover; counts, then the chunk's part of lims, then the writes.
+// Once per call: each query's segment of the hit buffer sorted, keys and distances emitted.
+static int range_exact(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan, const RangeOut& o) {
+    int r;
+    hipStream_t s = c.s;
+    const bool fused = plan.h1 && !h->range_force_fallback;
+    const int64_t qc = plan.qc, B = c.B;
+    const int64_t hcap = o.cap + h->n;  // a query that starts below cap holds all its hits (<= n)
+    if (hcap > (int64_t)0x7fffffff)
+        return fail(h, MHNSW_EUNSUPPORTED, "range search supports cap + rows < 2^31");
+    size_t tmp_bytes = 0;
+    LCHK(h, range_sort_temp_bytes(hcap, B, &tmp_bytes));
+    if ((r = ensure_buf(h, h->rthr, (size_t)qc)) || (r = ensure_buf(h, h->rstate, (size_t)qc)) ||
+        (r = ensure_buf(h, h->rsweep, (size_t)qc)) || (r = ensure_buf(h, h->rcnt, (size_t)qc)) ||
+        (r = ensure_buf(h, h->rcursor, (size_t)qc)) || (r = ensure_buf(h, h->rseg, (size_t)2 * B)) ||
+        (r = ensure_buf(h, h->rhits, (size_t)2 * hcap)) || (r = ensure_buf(h, h->rtmp, std::max<size_t>(tmp_bytes, 1))))
+        return r;
+    if (fused && h->xsplit_rows < h->n) {
+        if (h->xsplit_rows == 0) HIPCHK(h, hipMemsetAsync(h->xerr.p, 0, sizeof(float), s));
+        LCHK(h, launch_split_h16(h->vecs, h->xsplit_rows, h->n, h->pitch, h->capn, h->xsplit.p, nullptr, h->xinv.p,
+                                 h->xerr.p, s));
+        h->xsplit_rows = h->n;
+    }
+    if (h->metric == EUCLIDEAN) {
+        HIPCHK(h, hipMemsetAsync(h->xmaxn.p, 0, sizeof(float), s));
+        LCHK(h, launch_max_norm(h->norms, h->n, h->xmaxn.p, s));
+    }
+    for (int64_t q0 = 0; q0 < B; q0 += qc) {
+        const int64_t nb = std::min(qc, B - q0);
+        RangeArgs ra{};
+        ra.g = plan.g;
+        ra.Q = h->qpad.p + (size_t)q0 * h->pitch;
+        ra.radius = o.radius + q0;
+        ra.B = nb;
+        ra.qcnt = h->h1qcnt.p;
+        ra.bucket = h->h1bucket.p;
+        ra.scap = plan.scap;
+        ra.qovf = h->h1ovf.p;
+        ra.state = h->rstate.p;
+        ra.sweep = h->rsweep.p;
+        ra.cnt = h->rcnt.p;
+        ra.cursor = h->rcursor.p;
+        ra.lims = o.lims + q0;
+        ra.hits = h->rhits.p;
+        ra.hcap = hcap;
+        ra.cap = o.cap;
+        ra.stat = h->rstat.p;
+        CertArgs c1 = plan.cert;
+        c1.qnorm = h->qnorm.p + q0;
+        const bool mark0 = c.timing && q0 == 0;  // the stage marks: the first chunk's stages, and the order stage
+        if (mark0) HIPCHK(h, hipEventRecord(h->fxev[0], s));
+        if (fused) {
+            HIPCHK(h, hipMemsetAsync(h->qerr.p, 0, sizeof(float), s));
+            LCHK(h, launch_split_h16(ra.Q, 0, nb, h->pitch, qc, h->qsplit.p, nullptr, h->qinv.p, h->qerr.p, s));
+        }
+        // 1. the radius as the score threshold, and each query's path
+        LCHK(h, launch_range_thr(ra, c1.qnorm, fused ? h->qinv.p : nullptr, c1,
+                                 h->range_force_fallback ? -1 : fused ? 1 : 0, h->rthr.p, s));
+        if (fused) {
+            // 2. the filter GEMM and the per-query buckets, as the top-k search runs them
+            ExactArgs a{};
+            a.X = h->vecs;
+            a.xnorm = h->norms;
+            a.dead = plan.xdead;
+            a.N = h->n;
+            a.Q = ra.Q;
+            a.qnorm = c1.qnorm;
+            a.B = nb;
+            a.pitch = h->pitch;
+            a.dim = h->dim;
+            a.metric = h->metric;
+            a.Xh = h->xsplit.p;
+            a.Xl = h->xsplit.p + (size_t)h->capn * h->pitch;
+            a.ldXs = h->capn;
+            a.Qh = h->qsplit.p;
+            a.Ql = h->qsplit.p + (size_t)qc * h->pitch;
+            a.ldQs = qc;
+            a.xinv = h->xinv.p;
+            a.qinv = h->qinv.p;
+            LCHK(h, launch_ring_prep(h->rthr.p, a.qnorm, a.qinv, nb, h->metric, h->h1c.p, h->h1s.p, s));
+            HIPCHK(h, hipMemsetAsync(h->h1qcnt.p, 0, (size_t)nb * H1_BSUB * H1_CSTRIDE * 4, s));
+            HIPCHK(h, hipMemsetAsync(h->h1ovf.p, 0, (size_t)nb, s));
+            a.tile_stride = 1;
+            a.ring_c = h->h1c.p;
+            a.ring_s = h->h1s.p;
+            a.region = h->h1region.p;
+            a.region_cnt = h->h1rcnt.p;
+            a.rcap = plan.rcap;
+            a.xw = reinterpret_cast<const float4*>(h->h1xw.p);
+            if (q0 == 0)
+                LCHK(h, launch_h1_rowconst(a.xinv, a.xnorm, a.dead, a.N, h->metric, reinterpret_cast<float4*>(h->h1xw.p), s));
+            if (c.timing && q0 == 0) HIPCHK(h, hipEventRecord(h->gev0, s));
+            LCHK(h, launch_h1_filter(a, plan.ev, s));
+            if (c.timing && q0 == 0) {
+                HIPCHK(h, hipEventRecord(h->gev1, s));
+                h->have_gemm_timing = true;
+            }
+            const int64_t bqt = (nb + plan.bm - 1) / plan.bm;
+            LCHK(h, launch_bucket(h->h1region.p, h->h1rcnt.p, plan.rcap, bqt * plan.nnt, bqt, plan.bm, H1_BN, nb,
+                                  h->h1qcnt.p, h->h1bucket.p, plan.scap, h->h1ovf.p, plan.rsub,
+                                  h1_records(plan.ev) ? 1 : 0, a, s));
+            if (mark0) HIPCHK(h, hipEventRecord(h->fxev[1], s));
+            // 3. canonical check of the candidates, the hits compacted in their sub-buckets
+            LCHK(h, launch_range_refine(ra, h->lpr, h->vpl, s));
+        } else if (mark0) {
+            HIPCHK(h, hipEventRecord(h->fxev[1], s));
+        }
+        if (mark0) HIPCHK(h, hipEventRecord(h->fxev[2], s));
+        // 4. the sweep's count, the chunk's prefix, then the writes into the queries' segments
+        LCHK(h, launch_range_sweep(ra, h->n, plan.nseg, plan.seglen, false, h->lpr, h->vpl, s));
+        LCHK(h, launch_range_scan(h->rcnt.p, nb, ra.lims, h->rcursor.p, s));
+        if (fused) LCHK(h, launch_range_gather(ra, s));
+        LCHK(h, launch_range_sweep(ra, h->n, plan.nseg, plan.seglen, true, h->lpr, h->vpl, s));
+        if (mark0) HIPCHK(h, hipEventRecord(h->fxev[3], s));
+    }
+    if (c.timing) HIPCHK(h, hipEventRecord(h->fxev[4], s));
+    // 5. order each query's segment by (distance, row id) and emit
+    LCHK(h, launch_range_order_emit(h->rhits.p, h->rhits.p + hcap, hcap, o.lims, B, o.cap, h->rseg.p, h->rseg.p + B,
+                                    h->rtmp.p, tmp_bytes, plan.g, o.keys, o.dist, s));
+    if (c.timing) HIPCHK(h, hipEventRecord(h->fxev[5], s));
+    h->have_range_timing = c.timing;
+    if (fused && h1_timing_diag(plan.ev))
+        return fail(h, MHNSW_EUNSUPPORTED, "exact_tile %d is a timing diagnostic: no results", h->exact_tile);
+    return 0;
+}
+
+// The kernels of one range search, enqueued on c.s.  c.k is set here: 1 in exact mode (the
+// exact path's workspace sizing), ef in beam mode (the beam search's list).
+static int range_search(mhnsw_index* h, SearchCall& c, int mode, int ef, const RangeOut& o) {
+    int r = validate(h);
+    if (r) return r;
+    h->have_gemm_timing = false;
+    h->have_range_stats = false;
+    h->have_range_timing = false;
+    h->have_fx_timing = false;  // (the stage events are shared with the filtered exact search)
+    c.k = 1;
+    if ((r = check_args(h, c, mode))) return r;
+    if (mode == MHNSW_MODE_COMPAT) return fail(h, MHNSW_EUNSUPPORTED, "range search supports beam and exact mode");
+    if (o.cap < 0) return fail(h, MHNSW_EINVAL, "cap must be >= 0, got %lld", (long long)o.cap);
+    if (ef <= 0) ef = h->ef;
+    if (mode == MHNSW_MODE_BEAM && std::max(ef, 1) > 2048)
+        return fail(h, MHNSW_EUNSUPPORTED, "beam mode supports max(ef,k) <= 2048");
+    hipStream_t s = c.s;
+    if (c.B <= 0 || !h->layers_exist || live_count(h) == 0) {  // no query or no row: all-zero lims
+        HIPCHK(h, hipMemsetAsync(o.lims, 0, (size_t)(std::max<int64_t>(c.B, 0) + 1) * 8, s));
+        if (!c.sticky) HIPCHK(h, hipMemsetAsync(h->d_err, 0, sizeof(int), s));
+        return 0;
+    }
+    if (c.B > (int64_t)0x7fffffff) return fail(h, MHNSW_EUNSUPPORTED, "range search supports B < 2^31");
+    if ((r = ensure_buf(h, h->rstat, 2))) return r;
+    HIPCHK(h, hipMemsetAsync(h->rstat.p, 0, 16, s));
+    HIPCHK(h, hipMemsetAsync(o.lims, 0, 8, s));
+    const bool timing = c.timing;
+    c.timing = false;  // the call's own bracket, below, not the beam search's
+    if (mode == MHNSW_MODE_EXACT) {
+        if ((r = stage(h, c))) return r;
+        // like the filtered exact search, the call always scores at precision 3 (its results do
+        // not depend on the precision)
+        ExactPlan plan;
+        const RowSet every{h->n, h->capn, 3, nullptr, nullptr, 0};
+        if ((r = exact_prepare(h, c, every, plan, h->range_expect))) return r;
+        if (timing) HIPCHK(h, hipEventRecord(h->ev0, s));
+        c.timing = timing;
+        if ((r = range_exact(h, c, plan, o))) return r;
+    } else {
+        c.k = std::max(ef, 1);
+        const int top = top_live_layer(h);
+        // the beam lists go to the handle's scratch, whoever owns the queries
+        if ((r = ensure_buf(h, h->okeys, (size_t)c.B * c.k)) || (r = ensure_buf(h, h->odist, (size_t)c.B * c.k)) ||
+            (r = ensure_buf(h, h->on, (size_t)c.B)) || (r = ensure_buf(h, h->rcnt, (size_t)c.B)))
+            return r;
+        c.okeys = h->okeys.p;
+        c.odist = h->odist.p;
+        c.on = h->on.p;
+        if ((r = stage(h, c))) return r;
+        SearchArgs a;
+        if ((r = walk_args(h, c, top, (uint32_t)h->layers[top].entry, c.k, c.k >= h->beam_lds_min_ef, a))) return r;
+        if (timing) HIPCHK(h, hipEventRecord(h->ev0, s));
+        if ((r = beam_search(h, c, a))) return r;
+        LCHK(h, launch_range_beam(h->okeys.p, h->odist.p, h->on.p, c.k, o.radius, c.B, h->rcnt.p, o.lims, o.cap, o.keys,
+                                  o.dist, s));
+    }
+    if (timing) HIPCHK(h, hipEventRecord(h->ev1, s));
+    h->have_timing = timing;
+    h->have_range_stats = true;
+    h->stats_host[6] += c.B;
+    return 0;
+}
+
+int range_search_device_impl(mhnsw_index* h, const float* d_queries, int64_t B, int dim, const float* d_radius, int mode,
+                             int ef, int64_t cap, int64_t* d_lims, int64_t* d_keys, float* d_dist, hipStream_t s) {
+    SearchCall c{d_queries, true, B, dim, 1, nullptr, nullptr, nullptr, nullptr, s, true, true};
+    const RangeOut o{d_radius, cap, d_lims, d_keys, d_dist};
+    return on_scratch(h, s, [&] { return range_search(h, c, mode, ef, o); });
+}
+
+// The host-pointer call: the device call into the handle's result buffers; when the hits did
+// not fit, once more with room for exactly lims[B].  The results stay there for
+// mhnsw_range_results.
+int range_search_impl(mhnsw_index* h, const float* queries, int64_t B, int dim, const float* radius, int mode, int ef,
+                      int64_t* out_lims) {
+    hipStream_t s = h->stream;
+    h->range_total = -1;
+    return on_scratch(h, s, [&]() -> int {
+        int r;
+        const int64_t nb = std::max<int64_t>(B, 0);
+        if (nb > 0 && !radius) return fail(h, MHNSW_EINVAL, "radius must be non-NULL");
+        if (!out_lims) return fail(h, MHNSW_EINVAL, "out_lims must be non-NULL");
+        if ((r = ensure_buf(h, h->rrad, (size_t)std::max<int64_t>(nb, 1))) || (r = ensure_buf(h, h->rlims, (size_t)nb + 1)))
+            return r;
+        if (nb > 0) HIPCHK(h, hipMemcpyAsync(h->rrad.p, radius, (size_t)nb * 4, hipMemcpyHostToDevice, s));
+        const int64_t room = std::max<int64_t>(0, (int64_t)0x7fffffff - h->n);
+        int64_t cap = std::min(room, std::max<int64_t>({(int64_t)h->rkeys.n, 1024, nb * h->range_expect}));
+        for (int pass = 0;; ++pass) {
+            if ((r = ensure_buf(h, h->rkeys, (size_t)std::max<int64_t>(cap, 1))) ||
+                (r = ensure_buf(h, h->rdist, (size_t)std::max<int64_t>(cap, 1))))
+                return r;
+            SearchCall c{queries, false, B, dim, 1, nullptr, nullptr, nullptr, nullptr, s, false, true};
+            const RangeOut o{h->rrad.p, cap, h->rlims.p, h->rkeys.p, h->rdist.p};
+            if ((r = range_search(h, c, mode, ef, o))) return r;
+            HIPCHK(h, hipMemcpyAsync(out_lims, h->rlims.p, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost, s));
+            if ((r = read_error(h, s))) return r;
+            if (out_lims[nb] <= cap) break;
+            if (pass) return fail(h, MHNSW_EINTERNAL, "range search: %lld hits after room for %lld", (long long)out_lims[nb], (long long)cap);
+            h->stats_host[6] -= nb;  // one search, run twice
+            cap = out_lims[nb];
+        }
+        h->range_total = out_lims[nb];
+        return 0;
+    });
 }
 
 }  // namespace mhh

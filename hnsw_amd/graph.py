@@ -594,6 +594,55 @@ class Graph:
         ok, _, on = self.search_filtered_arrays(q, k, filter, ef=ef, route=route, mode=mode)
         return self._nodes(ok[0, : on[0]])
 
+    # -- range search: every row within a radius (mhnsw.h "Range search") ------------
+    @staticmethod
+    def _range_io(queries, radius, mode: int):
+        """the query matrix and the per-query radii of a host range search"""
+        if mode == MODE_COMPAT:
+            raise HnswError(-6, "range search supports beam and exact mode")
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        rad = np.asarray(radius, np.float32)
+        if rad.ndim > 1 or (rad.ndim == 1 and len(rad) != len(q)):
+            raise HnswError(-1, f"{rad.size} radii for {len(q)} queries")
+        return q, np.ascontiguousarray(np.broadcast_to(rad, (len(q),)))
+
+    def range_search_arrays(self, queries, radius, mode: int = MODE_EXACT, ef: int = 0):
+        """Every row within `radius` of each query -> (lims int64[B + 1], keys
+        int64[lims[B]], dist float32[lims[B]]): query b's hits are
+        [lims[b], lims[b + 1]), ascending by (distance, row).  A hit's canonical
+        distance is finite and <= the radius (inclusive; the square-rooted
+        distance for L2); a NaN or negative radius gives no hit.  radius: one
+        per query, or a scalar for all.  MODE_EXACT returns every hit;
+        MODE_BEAM the hits the beam search at k = ef finds (a count equal to ef
+        means the list was exhausted: raise ef or use MODE_EXACT)."""
+        q, rad = self._range_io(queries, radius, mode)
+        self._sync()
+        B, d = q.shape
+        lims = np.zeros(B + 1, np.int64)
+        self._check(load().mhnsw_range_search(self._h, _ptr(q, C.c_float), B, d, _ptr(rad, C.c_float), int(mode),
+                                              int(ef), _ptr(lims, C.c_int64)))
+        total = int(lims[B])
+        keys, dist = np.zeros(total, np.int64), np.zeros(total, np.float32)
+        self._check(load().mhnsw_range_results(self._h, _ptr(keys, C.c_int64), _ptr(dist, C.c_float), total))
+        return lims, keys, dist
+
+    def range_search_device(self, q_ptr: int, B: int, dim: int, radius_ptr: int, cap: int, lims_ptr: int,
+                            keys_ptr: int, dist_ptr: int, mode: int = MODE_EXACT, ef: int = 0, stream: int = 0):
+        """range_search_arrays on device buffers (radius float32[B], lims
+        int64[B + 1], keys int64[cap], dist float32[cap]), enqueued on `stream`
+        (no host sync).  lims always holds the true prefix; only the positions
+        below cap are written, so lims[B] > cap asks for a larger buffer."""
+        self._check(load().mhnsw_range_search_device(self._h, C.c_void_p(q_ptr), B, dim, C.c_void_p(radius_ptr),
+                                                     int(mode), int(ef), int(cap), C.c_void_p(lims_ptr),
+                                                     C.c_void_p(keys_ptr), C.c_void_p(dist_ptr), C.c_void_p(stream)))
+
+    def RangeSearch(self, near, radius: float, mode: int = MODE_EXACT, ef: int = 0) -> List[Node]:
+        q = np.asarray(near, np.float32).reshape(1, -1)
+        _, keys, _ = self.range_search_arrays(q, radius, mode=mode, ef=ef)
+        return self._nodes(keys)
+
     def _node(self, key) -> Node:
         v = self._values.get(key)
         if v is None:
@@ -892,6 +941,19 @@ def NewGraphWithConfig(m: int, ml: float, efSearch: int, distance) -> Graph:  # 
     check(load().mhnsw_create(_metric_of(distance), int(m), float(ml), int(efSearch), seed & (2**64 - 1),
                               C.byref(h)))  # validates before touching the device
     return Graph(M=m, Ml=ml, EfSearch=efSearch, Distance=distance, Rng=seed, _handle=h)
+
+
+def split_ragged(lims, *arrays) -> list:
+    """A range search's ragged result per query: lims int64[B + 1] and arrays
+    of lims[B] entries -> B tuples of slices (a list of slices for one array)."""
+    lims = np.asarray(lims, np.int64)
+    if lims.ndim != 1 or len(lims) < 1 or lims[0] != 0 or np.any(np.diff(lims) < 0):
+        raise ValueError("lims must be a non-decreasing prefix starting at 0")
+    for a in arrays:
+        if len(a) < lims[-1]:
+            raise ValueError(f"array of {len(a)} entries for {int(lims[-1])} hits")
+    rows = [tuple(a[lims[b]:lims[b + 1]] for a in arrays) for b in range(len(lims) - 1)]
+    return [r[0] for r in rows] if len(arrays) == 1 else rows
 
 
 def sweep_device(metric: int, q_ptr, X_ptr, n: int, dim: int, out_ptr, stream=0):

@@ -403,6 +403,35 @@ class Graph {  // graph.go:305-332
         return search_filtered(near, k, filter, 0, 0, true);
     }
 
+    // Range search (mhnsw.h "Range search"): every row whose canonical distance to `near` is
+    // finite and <= radius (inclusive), nearest first, with the distances.  MHNSW_MODE_EXACT
+    // returns every hit; MHNSW_MODE_BEAM the hits a beam search at k = ef finds (ef <= 0:
+    // EfSearch): as many as ef means the list was exhausted.
+    struct RangeHit {
+        Node<K> node;
+        float Distance;
+    };
+    std::pair<std::vector<RangeHit>, Error> RangeSearch(const Vector& near, float radius, int mode = MHNSW_MODE_EXACT,
+                                                        int ef = 0) {
+        sync();
+        const int have = Dims();
+        if (have && (int)near.size() != have)
+            return {{}, Error{"embedding dimension mismatch: " + std::to_string(have) + " != " +
+                                  std::to_string(near.size()),
+                              MHNSW_EDIM}};
+        int64_t lims[2] = {0, 0};
+        int rc = mhnsw_range_search(h_, near.data(), 1, (int)near.size(), &radius, mode, ef, lims);
+        if (rc < 0) return {{}, make_error(rc, h_)};
+        std::vector<int64_t> keys((size_t)lims[1]);
+        std::vector<float> dist((size_t)lims[1]);
+        rc = mhnsw_range_results(h_, keys.data(), dist.data(), lims[1]);
+        if (rc < 0) return {{}, make_error(rc, h_)};
+        std::vector<RangeHit> out;
+        const std::vector<K> ks = Codec::decode(h_, keys.data(), keys.size());
+        for (size_t i = 0; i < ks.size(); ++i) out.push_back(RangeHit{Node<K>{ks[i], lookup_value(ks[i])}, dist[i]});
+        return {out, {}};
+    }
+
    private:
     std::pair<std::vector<Node<K>>, Error> search_filtered(const Vector& near, int k, const Filter* filter, int ef,
                                                            int route, bool exact) {

@@ -285,6 +285,58 @@ int mhnsw_search_filtered_exact(mhnsw_index *h, const float *queries, int64_t B,
 int mhnsw_search_filtered_exact_device(mhnsw_index *h, const float *d_queries, int64_t B, int dim, int k, int filter,
                                        int64_t *d_keys, float *d_dist, int32_t *d_n, void *stream);
 
+/* ---- Range search: every row within a radius (faiss's range_search; DESIGN.md
+ * "Range search") ----
+ * For query b with radius radius[b], a row is a hit iff a MHNSW_MODE_EXACT search
+ * could return it (not deleted, not left partial by a failed insert), its
+ * canonical float32 distance d is finite, and d <= radius[b]: inclusive, on the
+ * canonical distance itself (for MHNSW_EUCLIDEAN the square-rooted one).  NaN and
+ * +inf distances are never hits; a NaN or negative radius gives zero hits and no
+ * error (the comparison is d <= r as it stands: the one distance a negative radius
+ * can admit is a cosine distance that rounded a few ulps below zero).  The result is ragged: lims[B + 1] is the exclusive prefix of the
+ * per-query counts, query b's hits occupy [lims[b], lims[b + 1]) of keys / dist,
+ * in ascending (distance, internal row id) order.
+ * MHNSW_MODE_EXACT returns every hit: the radius becomes the threshold of the
+ * exact mode's fp16 filter GEMM (the certificate's error bound added, so no hit
+ * is filtered out), the candidates are checked canonically, and queries the
+ * filter cannot cover (a bound that does not hold, an overflowed region or
+ * sub-bucket, fewer than 256 rows) are answered by a canonical sweep of every
+ * row.  The call always scores at exact_precision 3 (the results do not depend
+ * on the precision).  Option "range_expect" (default 64): the expected hits per
+ * query the filter's buffers are sized for; more hits only send queries to the
+ * sweep.  Works in every build mode, MHNSW_BUILD_FLAT included.
+ * MHNSW_MODE_BEAM returns the hits the beam search finds: it runs
+ * mhnsw_search's beam mode at k = ef (max(ef, 1) <= 2048, ef <= 0 uses EfSearch)
+ * and keeps the entries within the radius.  A per-query count equal to ef means
+ * the list was exhausted: raise ef or use MHNSW_MODE_EXACT.
+ * MHNSW_MODE_COMPAT fails with MHNSW_EUNSUPPORTED, "range search supports beam
+ * and exact mode".  An empty index or B <= 0 gives all-zero lims.
+ * mhnsw_range_search is synchronous: it writes out_lims and leaves the hits in a
+ * buffer the handle owns until the next range search or mutation;
+ * mhnsw_range_results copies them out (MHNSW_EINVAL when cap < lims[B]).  When
+ * the hits do not fit the handle's buffer the search runs a second time with
+ * room for exactly lims[B].
+ * mhnsw_range_search_device is enqueued on `stream` with the handle's workspace
+ * like mhnsw_search_device, without a host synchronisation: d_lims always holds
+ * the true prefix; a hit whose position is >= cap is not written (the positions
+ * below cap hold what a larger buffer would hold there); d_lims[B] > cap tells
+ * the caller to come back with a larger buffer.  Exact mode needs
+ * cap + rows < 2^31.  Read-only options: "last_range_candidates" ((query, row)
+ * pairs the filter passed on to the canonical check) and
+ * "last_range_fallback_queries" (queries the sweep answered); test option
+ * "range_force_fallback" (1: every query takes the sweep).
+ * mhnsw_last_kernel_ms covers the whole call (of a host call that ran twice,
+ * the second run); the read-only options last_range_filter_ns, last_range_refine_ns
+ * and last_range_sweep_ns (of the first chunk of queries) and last_range_order_ns
+ * (the call's sort and emit) split an exact-mode call.  Measured on 1M x 768
+ * cosine rows, batches of 16,384 (profiles/range_search.txt): 32.2 / 30.3 / 38.9 ms
+ * at 10 / 100 / 1,000 hits per query, against 35.2 ms for the exact top-10 search. */
+int mhnsw_range_search(mhnsw_index *h, const float *queries, int64_t B, int dim, const float *radius, int mode, int ef,
+                       int64_t *out_lims);
+int mhnsw_range_results(mhnsw_index *h, int64_t *out_keys, float *out_dist, int64_t cap);
+int mhnsw_range_search_device(mhnsw_index *h, const float *d_queries, int64_t B, int dim, const float *d_radius, int mode,
+                              int ef, int64_t cap, int64_t *d_lims, int64_t *d_keys, float *d_dist, void *stream);
+
 /* ---- SearchWithNegative(s) / BatchSearchWithNegatives (graph.go:1116-1537) ----
  * Query b's negatives are the next neg_count[b] rows of `negatives` (B*dim
  * queries, sum(neg_count)*dim negatives).  Candidates = Search(near,
