@@ -106,6 +106,11 @@ class ExactIndex:
     def BatchDelete(self, keys) -> List[bool]:  # exact.go:127-143
         return self._g.BatchDelete(keys)
 
+    def Compact(self) -> int:
+        """Reclaim the rows of deleted keys (Graph.Compact): searches return the same lists,
+        and the exact path stops scanning the deleted rows.  Returns the rows removed."""
+        return self._g.Compact()
+
     def Len(self) -> int:  # exact.go:146-151
         return self._g.Len()
 

@@ -1186,6 +1186,8 @@ void mhnsw_destroy(mhnsw_index* h) {
     if (h->scr_ev) (void)hipEventDestroy(h->scr_ev);
     if (h->meta_ev) (void)hipEventDestroy(h->meta_ev);
     if (h->ord_ev) (void)hipEventDestroy(h->ord_ev);
+    if (h->cev0) (void)hipEventDestroy(h->cev0);
+    if (h->cev1) (void)hipEventDestroy(h->cev1);
     if (h->ord_pin) (void)hipHostFree(h->ord_pin);
     for (auto e : h->tev) (void)hipEventDestroy(e);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1331,6 +1333,9 @@ int mhnsw_set_option(mhnsw_index* h, const char* name, int64_t v) {
     } else if (n == "filter_route") {
         if (v < 1 || v > 2048) return fail(h, MHNSW_EINVAL, "filter_route must be in [1, 2048]");
         h->filter_route = (int)v;
+    } else if (n == "compact_stage_rows") {
+        if (v < 1) return fail(h, MHNSW_EINVAL, "compact_stage_rows must be >= 1");
+        h->compact_stage_rows = v;
     } else if (n == "time_build") {
         h->time_build = (int)(v != 0);
     } else if (n == "max_rows") {
@@ -1427,6 +1432,19 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
         if (i == 5 || !h->have_fx_timing || hipEventSynchronize(h->fxev[i + 1]) != hipSuccess ||
             hipEventElapsedTime(&ms, h->fxev[i], h->fxev[i + 1]) != hipSuccess)
             return MHNSW_EINVAL;
+        *v = (int64_t)std::llround((double)ms * 1e6);
+    }
+    else if (n == "compact_stage_rows") *v = h->compact_stage_rows;
+    else if (n == "dead_rows") {  // read-only: rows flagged dead that still occupy storage
+        int64_t c = 0;
+        for (int64_t i = 0; i < h->n; ++i) c += h->hdead[i] != 0;
+        *v = c;
+    }
+    else if (n == "last_compact_dangling") *v = h->compact_dangling;            // read-only, of the last mhnsw_compact:
+    else if (n == "last_compact_scratch_bytes") *v = h->compact_scratch_bytes;  // edges dropped, bytes allocated,
+    else if (n == "last_compact_ns") {                                          // device time (HIP events)
+        float ms = 0.f;
+        if (!h->have_compact_timing || hipEventElapsedTime(&ms, h->cev0, h->cev1) != hipSuccess) return MHNSW_EINVAL;
         *v = (int64_t)std::llround((double)ms * 1e6);
     }
     else if (n == "range_expect") *v = h->range_expect;
@@ -1946,6 +1964,167 @@ int mhnsw_delete(mhnsw_index* h, const int64_t* keys, int64_t n, uint8_t* out) {
     if (err & 4) return fail(h, MHNSW_EINTERNAL, "out-of-range node id in adjacency (graph corrupt)");
     if (err & 8) return fail(h, MHNSW_EINTERNAL, "replenish candidate heap overflow");
     return 0;
+}
+
+// Compaction: the deleted rows leave the store, in place.  Live row i becomes row new(i) =
+// the live rows below it (monotone: the live rows keep their order, so every list ordered by
+// (distance, row id) stays what it was), n becomes the live count, the capacity stays and
+// the freed tail is what later Adds fill.
+//
+// The rows from the first deleted one on move in ascending chunks of destination rows on
+// the handle's stream.  A chunk whose destination ends at or below its first source row is
+// gathered straight into place: it overwrites only deleted rows and rows that earlier
+// chunks have read.  Any other chunk is gathered into the staging buffer and copied from
+// there.  Device memory beyond the index: the map and its inverse (4 bytes per row each)
+// and the stage, at most compact_stage_rows rows of the widest array -- never a second store.
+int mhnsw_compact(mhnsw_index* h, int64_t* out_removed) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    if (out_removed) *out_removed = 0;
+    if (h->build_mode == MHNSW_BUILD_COMPAT || h->aliased || h->partial_rows > 0)
+        return fail(h, MHNSW_EUNSUPPORTED, "compact needs a batch or flat (build_mode 1 or 2) handle");
+    int r = drain(h);
+    if (r) return r;
+    const int64_t n0 = h->n;
+    std::vector<int32_t> hnew((size_t)n0);  // the map, from the mirror of the bytes the device reads
+    int64_t live = 0, first = -1;
+    for (int64_t i = 0; i < n0; ++i) {
+        if (h->hdead[i] && first < 0) first = i;
+        hnew[i] = h->hdead[i] ? -1 : (int32_t)live++;
+    }
+    if (first < 0) return MHNSW_OK;  // nothing deleted: nothing written
+    // (the hits a host range search left behind are keys and distances: they stay valid, as
+    // they do across Add and Delete)
+    ++h->mut_epoch;
+    // the chunks: {first destination row, rows, staged}
+    struct Chunk {
+        int64_t d0, cnt;
+        bool staged;
+    };
+    std::vector<uint32_t> hsrc((size_t)live);
+    for (int64_t i = first; i < n0; ++i)
+        if (hnew[i] >= 0) hsrc[hnew[i]] = (uint32_t)i;
+    std::vector<Chunk> plan;
+    int64_t stage_rows = 0;
+    for (int64_t d = first; d < live;) {
+        const int64_t shift = (int64_t)hsrc[d] - d;  // deleted rows below this chunk's first source: >= 1
+        int64_t cnt = std::min(live - d, std::max(shift, h->compact_stage_rows));
+        const bool staged = d + cnt > (int64_t)hsrc[d];
+        if (staged) stage_rows = std::max(stage_rows, cnt);
+        plan.push_back({d, cnt, staged});
+        d += cnt;
+    }
+    // the arrays that hold a row each; member: the layer's deg for its adjacency arrays, which
+    // go before it (a direct chunk leaves out the rows that are not in the layer: nothing reads
+    // them; a staged one moves whole chunks, the stage holding no row of its own)
+    struct Arr {
+        void* p;
+        size_t row_bytes;
+        const int32_t* member = nullptr;
+    };
+    std::vector<Arr> arrs;
+    arrs.push_back({h->vecs, (size_t)h->pitch * 4});
+    if (h->h16) arrs.push_back({h->h16, (size_t)h->pitch * 2});
+    if (h->h16aux) arrs.push_back({h->h16aux, sizeof(float2)});
+    arrs.push_back({h->norms, 4});
+    arrs.push_back({h->keys, 8});
+    arrs.push_back({h->levels, 4});
+    for (auto& L : h->layers) {
+        arrs.push_back({L.adj, (size_t)L.cap * 4, L.deg});
+        arrs.push_back({L.adjd, (size_t)L.cap * 4, L.deg});
+        arrs.push_back({L.deg, 4});
+    }
+    size_t widest = 0;
+    for (auto& a : arrs) widest = std::max(widest, a.row_bytes);
+    // every allocation before the first move: filters over the capacity, events, map, stage
+    if ((r = filters_fit(h))) return r;
+    size_t fwords = 0;
+    for (auto& F : h->filters)
+        if (F.used) fwords = std::max(fwords, F.bits.size());
+    if (!h->cev0 && (hipEventCreate(&h->cev0) != hipSuccess || hipEventCreate(&h->cev1) != hipSuccess))
+        return fail(h, MHNSW_EDEVICE, "event creation failed");
+    // one block: newid [max(n0, fwords)] (later the repacked filter words), src [n0], the
+    // per-block counts, the dangling-edge counter
+    const size_t map_words = std::max((size_t)n0, fwords), nblk = (size_t)compact_blocks(n0);
+    const size_t map_bytes = (map_words + (size_t)n0 + nblk + 1) / 2 * 8 + 8;  // (the counter 8-byte aligned)
+    const size_t stage_bytes = (size_t)stage_rows * widest;
+    char *map = nullptr, *stage = nullptr;
+    if (hipMalloc(&map, map_bytes) != hipSuccess || (stage_bytes && hipMalloc(&stage, stage_bytes) != hipSuccess)) {
+        if (map) (void)hipFree(map);
+        return fail(h, MHNSW_ENOMEM, "device allocation of %zu bytes failed", map_bytes + stage_bytes);
+    }
+    int32_t* newid = reinterpret_cast<int32_t*>(map);
+    uint32_t* src = reinterpret_cast<uint32_t*>(map) + map_words;
+    uint32_t* blocks = src + n0;
+    unsigned long long* dangling = reinterpret_cast<unsigned long long*>(map + map_bytes - 8);
+    h->compact_scratch_bytes = (int64_t)(map_bytes + stage_bytes);
+    hipStream_t s = h->stream;
+    auto device_work = [&]() -> int {
+        HIPCHK(h, hipEventRecord(h->cev0, s));
+        HIPCHK(h, hipMemsetAsync(dangling, 0, 8, s));
+        LCHK(h, launch_compact_map(h->dead, n0, blocks, newid, src, s));
+        for (const Chunk& c : plan)
+            for (const Arr& a : arrs) {
+                char* dst = static_cast<char*>(a.p) + (size_t)c.d0 * a.row_bytes;
+                LCHK(h, launch_compact_rows(a.p, c.staged ? stage : dst, src + c.d0, c.cnt, a.row_bytes,
+                                         c.staged ? nullptr : a.member, s));
+                if (c.staged)
+                    HIPCHK(h, hipMemcpyAsync(dst, stage, (size_t)c.cnt * a.row_bytes, hipMemcpyDeviceToDevice, s));
+            }
+        // the freed tail as a grown store leaves it: absent in every layer, no links, not
+        // deleted; nothing pending in the insert's request counters
+        const size_t tail = (size_t)(n0 - live);
+        for (auto& L : h->layers) {
+            LCHK(h, launch_compact_adj(L.deg, L.adj, L.adjd, L.cap, live, newid, n0, dangling, s));
+            HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(L.deg + live), (int)0xFFFFFFFEu, tail, s));
+            HIPCHK(h, hipMemsetAsync(L.adj + (size_t)live * L.cap, 0xFF, tail * L.cap * 4, s));
+            HIPCHK(h, hipMemsetAsync(L.adjd + (size_t)live * L.cap, 0, tail * L.cap * 4, s));
+        }
+        HIPCHK(h, hipMemsetAsync(h->dead, 0, (size_t)h->capn, s));
+        HIPCHK(h, hipMemsetAsync(h->inc_cnt + live, 0, tail * 4, s));
+        // filters: repacked into the map's words (every id has gone through it by now), then
+        // back into the bitmap and its host mirror
+        for (auto& F : h->filters) {
+            if (!F.used) continue;
+            const size_t w = F.bits.size();
+            LCHK(h, launch_compact_filter(F.d, reinterpret_cast<uint32_t*>(newid), (int64_t)w, src, live, s));
+            HIPCHK(h, hipMemcpyAsync(F.d, newid, w * 4, hipMemcpyDeviceToDevice, s));
+            HIPCHK(h, hipMemcpyAsync(F.bits.data(), F.d, w * 4, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(h, hipEventRecord(h->cev1, s));
+        unsigned long long dang = 0;
+        HIPCHK(h, hipMemcpyAsync(&dang, dangling, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        h->compact_dangling = (int64_t)dang;
+        h->have_compact_timing = true;
+        return 0;
+    };
+    r = device_work();
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(map);
+    if (stage) (void)hipFree(stage);
+    if (r) return r;
+    // host mirrors.  Keys do not change: the string-key labels stay.
+    for (int64_t i = first; i < n0; ++i) {
+        if (hnew[i] < 0) continue;
+        h->hlevels[hnew[i]] = h->hlevels[i];
+        h->hmask[hnew[i]] = h->hmask[i];
+    }
+    h->hlevels.resize((size_t)live);
+    h->hmask.resize((size_t)live);
+    h->hdead.assign((size_t)live, 0);
+    for (auto& kv : h->key2id) kv.second = hnew[kv.second];
+    h->dead_kid.clear();  // (kids are row ids; only a compat handle reads them)
+    for (auto& L : h->layers) L.entry = L.count > 0 && L.entry >= 0 ? hnew[L.entry] : -1;  // (fix_entries: live)
+    h->n = live;
+    h->any_dead = false;
+    // per-row caches: the exact path's planes, unscales and rounding bound are rebuilt by the
+    // next exact search (its per-row filter constants are rebuilt by every search); the
+    // screening copy moved with the rows, and its error maximum over a superset stays valid
+    h->xsplit_rows = 0;
+    if ((r = sync_layer_entries(h))) return r;
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (out_removed) *out_removed = n0 - live;
+    return MHNSW_OK;
 }
 
 // analyzer.go:20-38 Connectivity: mean len(neighbors) per non-empty layer

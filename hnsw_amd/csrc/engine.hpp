@@ -327,6 +327,25 @@ int launch_rowset_gather(const uint16_t* src, int64_t ld_src, const uint32_t* id
 // cand[i] (a position in the row set, or EMPTY_ID) -> ids[cand[i]]
 int launch_rowset_remap(uint32_t* cand, int64_t total, const uint32_t* ids, int64_t m, hipStream_t s);
 
+// ---- compaction: the deleted rows leave the store in place (compact.hip) ----
+// newid[i] = live rows below i, -1 for a deleted row; src[newid[i]] = i (the live rows,
+// ascending); block_cnt [compact_blocks(n)] is the workspace.  n > 0 rows, n entries each.
+int64_t compact_blocks(int64_t n);
+int launch_compact_map(const uint8_t* dead, int64_t n, uint32_t* block_cnt, int32_t* newid, uint32_t* src,
+                       hipStream_t s);
+// rows ids[0 .. rows) of base (row_bytes each, a multiple of 4) -> rows 0 .. rows of dst,
+// which overlaps none of the rows read; member (nullable, a layer's deg indexed like base):
+// rows with member < 0 are left out
+int launch_compact_rows(const void* base, void* dst, const uint32_t* ids, int64_t rows, size_t row_bytes,
+                        const int32_t* member, hipStream_t s);
+// rows [0, rows) of a layer in place: every neighbour through newid, edges to deleted rows
+// dropped (row order kept, degree shrinks) and counted in *dangling
+int launch_compact_adj(int32_t* deg, int32_t* adj, float* adjd, int cap, int64_t rows, const int32_t* newid,
+                       int64_t n_old, unsigned long long* dangling, hipStream_t s);
+// out bit j = old bit src[j] for j < live, 0 above; nwords words each, out != old
+int launch_compact_filter(const uint32_t* old, uint32_t* out, int64_t nwords, const uint32_t* src, int64_t live,
+                          hipStream_t s);
+
 // certificate of the re-rank (nullable pieces disable it)
 struct CertArgs {
     const float* bound;          // [B] from k_select; nullptr = no certificate

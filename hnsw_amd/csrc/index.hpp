@@ -251,6 +251,12 @@ struct mhnsw_index {
     int64_t range_total = -1;  // hits the last host-pointer range search left in rkeys / rdist (-1: none)
     bool have_range_stats = false;
     bool have_range_timing = false;  // fxev holds an exact-mode range search's stage marks (options "last_range_*_ns")
+    // compaction (mhnsw_compact): rows per staged chunk (measured default: DESIGN.md §6 "Compaction"),
+    // and of the last call its event pair, device allocations and dropped edges to deleted rows
+    int64_t compact_stage_rows = 16384;
+    hipEvent_t cev0 = nullptr, cev1 = nullptr;
+    bool have_compact_timing = false;
+    int64_t compact_scratch_bytes = 0, compact_dangling = 0;
     std::string err;
     mutable std::shared_mutex mu;
 };

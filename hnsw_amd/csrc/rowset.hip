@@ -5,6 +5,7 @@
 // kernels: a bit test and a rank per row, 16-byte moves per row and K-block.
 #include <algorithm>
 
+#include "block_scan.hpp"
 #include "engine.hpp"
 
 namespace mh {
@@ -28,24 +29,6 @@ __device__ __forceinline__ uint32_t rs_dead_bits(const uint8_t* __restrict__ dea
     for (int j = 0; j < 32; ++j)  // the tail word: byte by byte, inside [0, n)
         if (r0 + j >= n || (dead && dead[r0 + j])) bits |= 1u << j;
     return bits;
-}
-
-// exclusive prefix of v over the block's 256 threads (4 waves) and the block's total
-__device__ __forceinline__ uint32_t rs_block_scan(uint32_t v, uint32_t& total) {
-    __shared__ uint32_t wsum[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int i = 0; i < w; ++i) base += wsum[i];
-    total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    return base + inc - v;
 }
 
 // Pass 1, one thread per bitmap word: the word's allowed rows (filter bit set, row below n and
@@ -79,16 +62,7 @@ __global__ __launch_bounds__(256) void k_rowset_words(const uint32_t* __restrict
 
 // Pass 2, one block: the exclusive prefix of the per-block counts, in place
 __global__ __launch_bounds__(256) void k_rowset_offsets(uint32_t* __restrict__ block_cnt, int64_t nblocks) {
-    uint32_t carry = 0;
-    for (int64_t b0 = 0; b0 < nblocks; b0 += 256) {
-        const int64_t b = b0 + threadIdx.x;
-        const uint32_t v = b < nblocks ? block_cnt[b] : 0u;
-        uint32_t total;
-        const uint32_t ex = rs_block_scan(v, total);
-        if (b < nblocks) block_cnt[b] = carry + ex;
-        carry += total;
-        __syncthreads();  // (rs_block_scan's LDS is reused by the next round)
-    }
+    rs_offsets_inplace(block_cnt, nblocks);
 }
 
 // Pass 3: a word's allowed rows at the block's offset + the word's rank in the block, in

@@ -814,6 +814,17 @@ class Graph:
                 self._values.pop(key, None)
         return res
 
+    # -- compaction ---------------------------------------------------------------
+    def Compact(self) -> int:
+        """Remove the deleted rows from the device store, in place (mhnsw_compact): the live
+        rows keep their order, so every search returns what it returned before, the filters
+        stay valid and the freed rows are what later Adds fill.  Returns the rows removed.
+        Batch and flat build modes only."""
+        self._sync()
+        removed = C.c_int64()
+        self._check(load().mhnsw_compact(self._h, C.byref(removed)))
+        return removed.value
+
     # -- levels / stats / exchange ------------------------------------------------
     def preview_levels(self, n: int) -> np.ndarray:
         out = np.zeros(n, np.int32)

@@ -528,6 +528,17 @@ class Graph {  // graph.go:305-332
         return res;
     }
 
+    // Compaction (mhnsw.h "Compaction"): the deleted rows leave the device store in place;
+    // searches, filters and keys are unchanged.  Returns the rows removed.  Batch and flat
+    // build modes only (MHNSW_EUNSUPPORTED otherwise).
+    std::pair<int64_t, Error> Compact() {
+        sync();
+        int64_t removed = 0;
+        const int rc = mhnsw_compact(h_, &removed);
+        if (rc < 0) return {0, make_error(rc, h_)};
+        return {removed, {}};
+    }
+
    private:
     // nodes[0, n) of dimension d through mhnsw_add, levels drawn as the walk goes
     Error addWalk(const std::vector<Node<K>>& nodes, size_t n, size_t d, const std::vector<int32_t>* levels) {

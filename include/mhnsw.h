@@ -380,6 +380,24 @@ int mhnsw_delete(mhnsw_index *h, const int64_t *keys, int64_t n, uint8_t *out);
  * written unless every argument is valid. */
 int mhnsw_replace(mhnsw_index *h, const int64_t *keys, const float *vecs, int64_t n, int dim, uint8_t *out);
 
+/* ---- Compaction ----
+ * Removes every deleted row from the handle's storage, on the device and in
+ * place: live row i becomes row new(i) = the live rows below it, so the live
+ * rows keep their order and every search returns the keys, distance bits and
+ * counts it returned before.  Afterwards the stored rows are the live ones,
+ * the capacity is unchanged (the freed tail is what later Adds fill), every
+ * filter keeps its id and its rows, and the export is the old one without the
+ * deleted rows, its ids renumbered.  *out_removed (nullable) = rows dropped;
+ * with nothing deleted the call writes nothing.  BATCH and FLAT build modes
+ * only: a COMPAT handle (whose deleted rows stay reachable), one with a
+ * replaced or re-added key or with rows a failed insert left outside layer 0
+ * fails with MHNSW_EUNSUPPORTED and is left as it was.  Device memory beyond
+ * the index: 8 bytes per stored row and a staging buffer of at most
+ * "compact_stage_rows" rows (option); MHNSW_ENOMEM leaves the index as it was.
+ * Read-only options: "dead_rows", "last_compact_ns", "last_compact_dangling",
+ * "last_compact_scratch_bytes". */
+int mhnsw_compact(mhnsw_index *h, int64_t *out_removed);
+
 /* ---- DistanceFunc (distance.go:12-23): batched sweep of one query over n rows ---- */
 int mhnsw_distance(int metric, const float *q, const float *X, int64_t n, int dim, float *out);
 int mhnsw_distance_device(int metric, const float *d_q, const float *d_X, int64_t n, int dim, float *d_out,
