@@ -360,7 +360,11 @@ int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t e
     const int efc = h->efc > 0 ? h->efc : h->ef;
     const int64_t nb = a1 - a0;
     std::vector<int64_t> count(MH_MAXL + 1, 0);  // nodes with level >= l
+    for (int64_t i = a0; i < a1; ++i) count[std::min(h->hlevels[i], MH_MAXL)]++;
+    for (int l = MH_MAXL - 1; l >= 0; --l) count[l] += count[l + 1];
     const bool fuse = h->fuse_descent != 0;
+    // batch_link: the layers whose launch covers at least two batch rows get the link pass
+    const bool link = h->batch_link != 0 && nb >= 2;
     if (fuse) {
         if (h->ord_cap < nb) {
             if (h->ord_pin) (void)hipHostFree(h->ord_pin);
@@ -372,8 +376,6 @@ int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t e
         }
         if ((r = ensure_buf(h, h->border, (size_t)nb))) return r;
         if (h->ord_pending) HIPCHK(h, hipEventSynchronize(h->ord_ev));  // the previous batch's copy has read ord_pin
-        for (int64_t i = a0; i < a1; ++i) count[std::min(h->hlevels[i], MH_MAXL)]++;
-        for (int l = MH_MAXL - 1; l >= 0; --l) count[l] += count[l + 1];
         std::vector<int64_t> pos(MH_MAXL + 1, 0);  // level-descending, stable within a level
         for (int l = 0; l <= MH_MAXL; ++l) pos[l] = l < MH_MAXL ? count[l + 1] : 0;
         for (int64_t i = a0; i < a1; ++i) h->ord_pin[pos[std::min(h->hlevels[i], MH_MAXL)]++] = (uint32_t)i;
@@ -381,6 +383,14 @@ int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t e
         HIPCHK(h, hipEventRecord(h->ord_ev, h->stream));
         h->ord_pending = true;
     }
+    // the compact visited set where it holds more than the 32-bit one in about the
+    // same LDS, for searches wide enough to fill that (efConstruction > 128;
+    // at efC 64 the plain set never fills and its probe is cheaper)
+    // (only in place of the 2^12-entry set: the LDS batch_lds sizes is the same
+    // 16 KiB; a larger vis_log2 keeps the larger 32-bit set the user asked for)
+    auto vis16_for = [&](int ef) -> int {
+        return h->vis_compact && ef > 128 && h->capn <= (int64_t(1) << 24) && h->vis_log2 == 12;
+    };
     auto args = [&](int l) {
         const int mcap = l == 0 ? m0_of(h) : h->M;
         BatchBuildArgs a;
@@ -409,12 +419,7 @@ int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t e
         a.stats = h->d_stats + 4;
         a.vis_log2 = h->vis_log2;
         a.mw_max = h->build_mw_max;
-        // the compact visited set where it holds more than the 32-bit one in about the
-        // same LDS, for searches wide enough to fill that (efConstruction > 128;
-        // at efC 64 the plain set never fills and its probe is cheaper)
-        // (only in place of the 2^12-entry set: the LDS batch_lds sizes is the same
-        // 16 KiB; a larger vis_log2 keeps the larger 32-bit set the user asked for)
-        a.vis16 = h->vis_compact && a.ef > 128 && h->capn <= (int64_t(1) << 24) && h->vis_log2 == 12;
+        a.vis16 = vis16_for(a.ef);
         return a;
     };
     // time_build: HIP events around every insert kernel (descent, layer searches, commits)
@@ -426,6 +431,16 @@ int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t e
             h->tev.push_back(e);
         }
         HIPCHK(h, hipEventRecord(h->tev[h->tev_used++], h->stream));
+        return 0;
+    };
+    auto lmark = [&]() -> int {  // (the link passes' own pairs: last_link_ns)
+        if (!h->time_build) return 0;
+        if (h->ltev_used == h->ltev.size()) {
+            hipEvent_t e;
+            HIPCHK(h, hipEventCreate(&e));
+            h->ltev.push_back(e);
+        }
+        HIPCHK(h, hipEventRecord(h->ltev[h->ltev_used++], h->stream));
         return 0;
     };
     for (int l = top; l >= 0; --l) {
@@ -446,6 +461,29 @@ int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t e
         LCHK(h, launch_build_batch_search(a, h->lpr, h->vpl, h->stream));
         if (maxlvl >= l) LCHK(h, launch_build_batch_commit(a, h->lpr, h->vpl, (a1 - a0) * mcap, h->stream));
         if ((r = tmark())) return r;
+        if (link && count[std::min(l, MH_MAXL)] >= 2) {
+            // The link pass: the layer now holds the batch, so its rows search it once more
+            // (from the nearest row their insert search found: cur_entry is read, not written
+            // -- the next layer's search starts there), stage their new rows, and the commit
+            // merges the reverse proposals into the touched batch rows.
+            if ((size_t)nb > h->link_cap || h->link_stride < h->layers[l].cap)
+                return fail(h, MHNSW_EINTERNAL, "link staging too small");
+            BatchBuildArgs la = a;
+            la.ef = h->batch_link_ef > 0 ? std::min(std::max(h->batch_link_ef, mcap), 512) : a.ef;
+            la.vis16 = vis16_for(la.ef);
+            LinkArgs k;
+            k.adj = h->link_adj;
+            k.adjd = h->link_adjd;
+            k.deg = h->link_deg;
+            k.stride = h->link_stride;
+            k.cnt = h->link_cnt;
+            HIPCHK(h, hipMemsetAsync(h->touched_cnt, 0, 4, h->stream));
+            if ((r = lmark())) return r;
+            LCHK(h, launch_build_batch_link(la, k, h->lpr, h->vpl, h->stream));
+            LCHK(h, launch_build_batch_link_apply(la, k, h->stream));
+            LCHK(h, launch_build_batch_commit(la, h->lpr, h->vpl, (a1 - a0) * mcap, h->stream));
+            if ((r = lmark())) return r;
+        }
     }
     return 0;
 }
@@ -464,6 +502,30 @@ int run_build_batch(mhnsw_index* h, int64_t n0, int64_t n1, int top, uint32_t en
         if (h->touched) (void)hipFree(h->touched);
         if (hipMalloc(&h->touched, tneed * 4) != hipSuccess) return fail(h, MHNSW_ENOMEM, "device allocation failed");
         h->touched_cap = tneed;
+    }
+    if (h->batch_link) {  // the link pass's staging rows, grown like `touched`, and its counters
+        int stride = std::max(cap_of(h, 0), cap_of(h, 1));
+        for (const Layer& L : h->layers) stride = std::max(stride, L.cap);
+        if (h->link_cap < (size_t)h->batch_max || h->link_stride < stride) {
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            if (h->link_adj) (void)hipFree(h->link_adj);
+            if (h->link_adjd) (void)hipFree(h->link_adjd);
+            if (h->link_deg) (void)hipFree(h->link_deg);
+            h->link_adj = nullptr;
+            h->link_adjd = nullptr;
+            h->link_deg = nullptr;
+            h->link_cap = 0;
+            const size_t rows = (size_t)h->batch_max;
+            if (hipMalloc(&h->link_adj, rows * stride * 4) != hipSuccess ||
+                hipMalloc(&h->link_adjd, rows * stride * 4) != hipSuccess ||
+                hipMalloc(&h->link_deg, rows * 4) != hipSuccess)
+                return fail(h, MHNSW_ENOMEM, "device allocation failed");
+            h->link_cap = rows;
+            h->link_stride = stride;
+        }
+        if (!h->link_cnt && hipMalloc(&h->link_cnt, 2 * sizeof(unsigned long long)) != hipSuccess)
+            return fail(h, MHNSW_ENOMEM, "device allocation failed");
+        HIPCHK(h, hipMemsetAsync(h->link_cnt, 0, 2 * sizeof(unsigned long long), h->stream));
     }
     int64_t i = n0;
     while (i < n1) {
@@ -494,8 +556,13 @@ int run_build_batch(mhnsw_index* h, int64_t n0, int64_t n1, int top, uint32_t en
     }
     int err = 0;
     HIPCHK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    unsigned long long lcnt[2] = {0, 0};
+    if (h->batch_link)
+        HIPCHK(h, hipMemcpyAsync(lcnt, h->link_cnt, sizeof(lcnt), hipMemcpyDeviceToHost, h->stream));
     if (while_gpu) while_gpu();  // host work that overlaps the last batches' kernels
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->link_rows += (int64_t)lcnt[0];
+    h->link_edges += (int64_t)lcnt[1];
     if (err & 4) return fail(h, MHNSW_EINTERNAL, "out-of-range node id in adjacency (graph corrupt)");
     return 0;
 }
@@ -1013,6 +1080,13 @@ int add_step(mhnsw_index* h, const int64_t* keys, const float* vecs, bool vecs_o
         h->build_search_us += ms * 1e3;
     }
     h->tev_used = 0;
+    for (size_t i = 0; i + 1 < h->ltev_used; i += 2) {
+        float ms = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ltev[i], h->ltev[i + 1]));
+        h->build_search_us += ms * 1e3;
+        h->link_us += ms * 1e3;
+    }
+    h->ltev_used = 0;
     if (r == 0) *reached = nproc;
     *cont_out = cont;
     return r;
@@ -1021,6 +1095,8 @@ int add_step(mhnsw_index* h, const int64_t* keys, const float* vecs, bool vecs_o
 int add_impl(mhnsw_index* h, const int64_t* keys, const float* vecs, bool vecs_on_device, int64_t n, int dim,
              const int32_t* levels) {
     h->add_reached = 0;
+    h->link_rows = h->link_edges = 0;
+    h->link_us = 0;
     for (;;) {
         int64_t reached = 0, cont = -1;
         const int r = add_step(h, keys, vecs, vecs_on_device, n, dim, levels, &reached, &cont);
@@ -1103,6 +1179,10 @@ void mhnsw_destroy(mhnsw_index* h) {
     F(h->inc_dist);
     F(h->touched);
     F(h->touched_cnt);
+    F(h->link_adj);
+    F(h->link_adjd);
+    F(h->link_deg);
+    F(h->link_cnt);
     F(h->d_layer_entry);
     F(h->d_layers);
     F(h->d_stats);
@@ -1190,6 +1270,7 @@ void mhnsw_destroy(mhnsw_index* h) {
     if (h->cev1) (void)hipEventDestroy(h->cev1);
     if (h->ord_pin) (void)hipHostFree(h->ord_pin);
     for (auto e : h->tev) (void)hipEventDestroy(e);
+    for (auto e : h->ltev) (void)hipEventDestroy(e);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->gev0) (void)hipEventDestroy(h->gev0);
@@ -1255,6 +1336,12 @@ int mhnsw_set_option(mhnsw_index* h, const char* name, int64_t v) {
     } else if (n == "upper_efc") {
         if (v < 0 || v > 512) return fail(h, MHNSW_EINVAL, "upper_efc must be in [0, 512]");
         h->upper_efc = (int)v;
+    } else if (n == "batch_link") {
+        if (v != 0 && v != 1) return fail(h, MHNSW_EINVAL, "batch_link must be 0 or 1");
+        h->batch_link = (int)v;
+    } else if (n == "batch_link_ef") {
+        if (v < 0) return fail(h, MHNSW_EINVAL, "batch_link_ef must be >= 0");
+        h->batch_link_ef = (int)std::min<int64_t>(v, 512);
     } else if (n == "search_expand") {
         if (v != 1 && v != 2 && v != 4) return fail(h, MHNSW_EINVAL, "search_expand must be 1, 2 or 4");
         h->search_expand = (int)v;
@@ -1391,6 +1478,14 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
     else if (n == "search_order_fields") *v = h->search_order_fields;
     else if (n == "search_order_map") *v = h->search_order_map;
     else if (n == "upper_efc") *v = h->upper_efc;
+    else if (n == "batch_link") *v = h->batch_link;
+    else if (n == "batch_link_ef") *v = h->batch_link_ef;
+    // read-only, of the last Add's link passes: rows (one per layer) whose selection changed, the batch-mates
+    // those selections added (counted as selected: the commit's overflow rule may prune one again, and the
+    // reverse edges the proposals add are not counted), the kernels' device time (time_build; else 0)
+    else if (n == "last_link_rows") *v = h->link_rows;
+    else if (n == "last_link_edges") *v = h->link_edges;
+    else if (n == "last_link_ns") *v = (int64_t)std::llround(h->link_us * 1e3);
     else if (n == "prune_alpha_pct") *v = h->alpha_pct;
     else if (n == "batch_min") *v = h->batch_min;
     else if (n == "batch_max") *v = h->batch_max;

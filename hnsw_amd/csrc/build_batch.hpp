@@ -143,6 +143,113 @@ __global__ __launch_bounds__(64) void k_batch_descend(BatchBuildArgs a) {
     }
 }
 
+// The neighbour selection of one row from its candidate list L (the first nl
+// entries, ranked by (distance, id)): up to a.mcap live candidates, by HNSW's
+// diversity rule when a.heuristic is set (a.alpha its slack), then
+// a.keep_pruned's fill.  Lane j < the count returned holds the j-th neighbour
+// in sel / seld.  Used by the insert (batch_insert) and by the link pass
+// (build_link.hpp k_batch_link).
+template <class C, int R, int G, bool SCREEN>
+__device__ __forceinline__ int select_neighbours(const BatchBuildArgs& a, const BList<R>& L, int nl, uint32_t& sel,
+                                                 float& seld, WaveStats& st) {
+    const int lane = lane_id();
+    bool sel_screen = false;
+    float margin = 0.f;
+    if constexpr (SCREEN) {
+        sel_screen = a.g.h16 != nullptr && a.alpha > 0.f;
+        const float e = a.g.h16err ? *a.g.h16err : 0.00048828125f;
+        margin = a.g.metric == EUCLIDEAN ? h16_margin_l2(e) : h16_margin_cos(e);
+    }
+    int nsel = 0;
+    // Screened: the same rule applied kept-row-major.  A candidate is kept
+    // iff no kept row before it drops it, so each kept row r can be applied
+    // at once to every later candidate still standing (one batched
+    // two-sided screen of their fp16 rows, r's f32 row the query, and the
+    // undecided pairs in f32); the next candidate standing is kept.
+    // d(c, r) == d(r, c) bitwise (commutative products, norms multiplied
+    // both ways round), so every decision is the candidate-major loop's
+    // below (the unscreened path): the same graph (test_gpu_screen.py
+    // compares with screen 0).  A candidate meets kept rows only until the
+    // first one drops it, and the kept rows, not the candidates, are read
+    // in f32: 15.4k -> 10.0k pair evaluations and 1.38k -> 0.99k f32 rows
+    // per insert on the bench index.
+    const bool rowmajor = SCREEN && sel_screen && a.heuristic;
+    if (rowmajor) {
+        uint32_t live = 0u, dropped = 0u;  // bit r: entry r * 64 + lane
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (L.i[r] != EMPTY_ID && r * 64 + lane < nl && !is_dead(a.g, L.i[r] & ID_MASK)) live |= 1u << r;
+        int pos = 0;
+        while (nsel < a.mcap) {
+            int idx = -1;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const unsigned long long m = __ballot(((live & ~dropped) >> r & 1u) && r * 64 + lane >= pos);
+                if (idx < 0 && m) idx = r * 64 + __ffsll((long long)m) - 1;
+            }
+            if (idx < 0) break;
+            float dc;
+            uint32_t c;
+            bl_at(L, idx, dc, c);
+            c &= ID_MASK;
+            if (lane == nsel) {
+                sel = c;
+                seld = dc;
+            }
+            ++nsel;
+            pos = idx + 1;
+            if (nsel >= a.mcap) break;
+            QReg<C> qr;
+            load_query(qr, a.g.vecs + (size_t)c * a.g.pitch);
+            drop_pass<C, G, R>(a.g, qr, a.g.norms[c], pos, live, dropped, L.i, L.d, a.alpha, margin, st);
+        }
+    }
+    for (int i = 0; !rowmajor && i < nl && nsel < a.mcap; ++i) {
+        float dc;
+        uint32_t c;
+        bl_at(L, i, dc, c);
+        if (c == EMPTY_ID) break;
+        c &= ID_MASK;
+        if (is_dead(a.g, c)) continue;
+        bool good = true;
+        if (a.heuristic && nsel > 0) {  // HNSW Alg. 4: drop c if closer to a kept neighbour than to u
+            QReg<C> qc;
+            load_query(qc, a.g.vecs + (size_t)c * a.g.pitch);
+            const float cn = a.g.norms[c];
+            st.E += nsel;
+            auto rule = [&](float dcs, uint32_t) {
+                if (a.alpha * dcs < dc) good = false;
+            };
+            st.F += nsel + 1;  // the candidate's row and the kept rows, in f32
+            eval_list<C, G>(a.g, qc, cn, sel, nsel, a.g.metric, rule);
+        }
+        if (good) {
+            if (lane == nsel) {
+                sel = c;
+                seld = dc;
+            }
+            ++nsel;
+        }
+    }
+    if (a.keep_pruned && nsel < a.mcap) {  // Malkov Alg. 4 keepPrunedConnections
+        for (int i = 0; i < nl && nsel < a.mcap; ++i) {
+            float dc;
+            uint32_t c;
+            bl_at(L, i, dc, c);
+            if (c == EMPTY_ID) break;
+            c &= ID_MASK;
+            if (is_dead(a.g, c)) continue;
+            if (__ballot(lane < nsel && sel == c)) continue;
+            if (lane == nsel) {
+                sel = c;
+                seld = dc;
+            }
+            ++nsel;
+        }
+    }
+    return nsel;
+}
+
 #ifndef MH_BUILD_WPS
 #define MH_BUILD_WPS 1
 #endif
@@ -176,103 +283,9 @@ __device__ __forceinline__ void batch_insert(const BatchBuildArgs& a, uint32_t u
         bl_at(L, 0, d0, i0);
         if (lane == 0 && i0 != EMPTY_ID) a.cur_entry[u] = i0 & ID_MASK;
         // neighbour selection
-        bool sel_screen = false;
-        float margin = 0.f;
-        if constexpr (SCREEN) {
-            sel_screen = a.g.h16 != nullptr && a.alpha > 0.f;
-            const float e = a.g.h16err ? *a.g.h16err : 0.00048828125f;
-            margin = a.g.metric == EUCLIDEAN ? h16_margin_l2(e) : h16_margin_cos(e);
-        }
         uint32_t sel = 0;
         float seld = 0.f;
-        int nsel = 0;
-        const int nl = a.ef;
-        // Screened: the same rule applied kept-row-major.  A candidate is kept
-        // iff no kept row before it drops it, so each kept row r can be applied
-        // at once to every later candidate still standing (one batched
-        // two-sided screen of their fp16 rows, r's f32 row the query, and the
-        // undecided pairs in f32); the next candidate standing is kept.
-        // d(c, r) == d(r, c) bitwise (commutative products, norms multiplied
-        // both ways round), so every decision is the candidate-major loop's
-        // below (the unscreened path): the same graph (test_gpu_screen.py
-        // compares with screen 0).  A candidate meets kept rows only until the
-        // first one drops it, and the kept rows, not the candidates, are read
-        // in f32: 15.4k -> 10.0k pair evaluations and 1.38k -> 0.99k f32 rows
-        // per insert on the bench index.
-        const bool rowmajor = SCREEN && sel_screen && a.heuristic;
-        if (rowmajor) {
-            uint32_t live = 0u, dropped = 0u;  // bit r: entry r * 64 + lane
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-                if (L.i[r] != EMPTY_ID && r * 64 + lane < nl && !is_dead(a.g, L.i[r] & ID_MASK)) live |= 1u << r;
-            int pos = 0;
-            while (nsel < a.mcap) {
-                int idx = -1;
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const unsigned long long m = __ballot(((live & ~dropped) >> r & 1u) && r * 64 + lane >= pos);
-                    if (idx < 0 && m) idx = r * 64 + __ffsll((long long)m) - 1;
-                }
-                if (idx < 0) break;
-                float dc;
-                uint32_t c;
-                bl_at(L, idx, dc, c);
-                c &= ID_MASK;
-                if (lane == nsel) {
-                    sel = c;
-                    seld = dc;
-                }
-                ++nsel;
-                pos = idx + 1;
-                if (nsel >= a.mcap) break;
-                QReg<C> qr;
-                load_query(qr, a.g.vecs + (size_t)c * a.g.pitch);
-                drop_pass<C, G, R>(a.g, qr, a.g.norms[c], pos, live, dropped, L.i, L.d, a.alpha, margin, st);
-            }
-        }
-        for (int i = 0; !rowmajor && i < nl && nsel < a.mcap; ++i) {
-            float dc;
-            uint32_t c;
-            bl_at(L, i, dc, c);
-            if (c == EMPTY_ID) break;
-            c &= ID_MASK;
-            if (is_dead(a.g, c)) continue;
-            bool good = true;
-            if (a.heuristic && nsel > 0) {  // HNSW Alg. 4: drop c if closer to a kept neighbour than to u
-                QReg<C> qc;
-                load_query(qc, a.g.vecs + (size_t)c * a.g.pitch);
-                const float cn = a.g.norms[c];
-                st.E += nsel;
-                auto rule = [&](float dcs, uint32_t) {
-                    if (a.alpha * dcs < dc) good = false;
-                };
-                st.F += nsel + 1;  // the candidate's row and the kept rows, in f32
-                eval_list<C, G>(a.g, qc, cn, sel, nsel, a.g.metric, rule);
-            }
-            if (good) {
-                if (lane == nsel) {
-                    sel = c;
-                    seld = dc;
-                }
-                ++nsel;
-            }
-        }
-        if (a.keep_pruned && nsel < a.mcap) {  // Malkov Alg. 4 keepPrunedConnections
-            for (int i = 0; i < nl && nsel < a.mcap; ++i) {
-                float dc;
-                uint32_t c;
-                bl_at(L, i, dc, c);
-                if (c == EMPTY_ID) break;
-                c &= ID_MASK;
-                if (is_dead(a.g, c)) continue;
-                if (__ballot(lane < nsel && sel == c)) continue;
-                if (lane == nsel) {
-                    sel = c;
-                    seld = dc;
-                }
-                ++nsel;
-            }
-        }
+        const int nsel = select_neighbours<C, R, G, SCREEN>(a, L, a.ef, sel, seld, st);
         const int capl = a.g.layers[l].cap;
         if (lane < nsel) {
             a.g.layers[l].adj[(size_t)u * capl + lane] = (int32_t)sel;

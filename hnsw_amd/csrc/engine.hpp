@@ -234,6 +234,19 @@ int launch_build_batch_search(const BatchBuildArgs& a, int lpr, int vpl, hipStre
 // greedy descent of every node u in [n0, n1) through layers a.layer .. levels[u] + 1
 int launch_build_batch_descend(const BatchBuildArgs& a, int lpr, int vpl, hipStream_t s);
 int launch_build_batch_commit(const BatchBuildArgs& a, int lpr, int vpl, int64_t n_touched, hipStream_t s);
+// The link pass (option "batch_link", build_link.hpp), after layer a.layer's commit: every
+// batch row of the layer searches it again (a.ef: the link width) and stages its new row
+// here; the reverse proposals go to a.inc_* / a.touched.  Rows are indexed by u - a.n0.
+struct LinkArgs {
+    int32_t* adj;             // [batch rows * stride] staged rows
+    float* adjd;              // [batch rows * stride] their distances
+    int32_t* deg;             // [batch rows] staged degree, -1: the row stays as it is
+    int stride;               // >= the layer's row cap
+    unsigned long long* cnt;  // [0] += rows staged, [1] += batch-mates new to their rows
+};
+int launch_build_batch_link(const BatchBuildArgs& a, const LinkArgs& k, int lpr, int vpl, hipStream_t s);
+// the staged rows -> the adjacency (then launch_build_batch_commit merges the proposals)
+int launch_build_batch_link_apply(const BatchBuildArgs& a, const LinkArgs& k, hipStream_t s);
 
 // ---- exact / merge ----
 // Brute-force path: approximate scores on MFMA (f32-input, or the bf16x3 split

@@ -102,10 +102,24 @@ struct mhnsw_index {
     int screen = 1;           // beam search / batched insert fp16 screening copy (results unchanged)
     int fuse_descent = 1;     // batched insert: all greedy descents of a batch in one launch (same graph)
     int time_build = 0;       // batched insert: time its search kernels with HIP events (stats [12])
+    int batch_link = 0;       // batched insert: after a layer's commit the batch's rows search it again and link to each other
+    int batch_link_ef = 0;    // ... the width of that search (0 = the layer's insert width; else clamped to [row cap, 512])
     int64_t max_rows = 0;     // row capacity limit (0 = none): an Add past it fails with MHNSW_ENOMEM, index unchanged
     std::vector<hipEvent_t> tev;  // event pairs around the timed launches of the current Add
     size_t tev_used = 0;
+    std::vector<hipEvent_t> ltev;  // ... and around its link passes
+    size_t ltev_used = 0;
     double build_search_us = 0;
+    // link pass: staged rows of the current batch (run_build_batch sizes them like `touched`), the device
+    // counters {rows staged, batch-mates written} and, of the last Add, their sums and the kernels' time
+    int32_t* link_adj = nullptr;
+    float* link_adjd = nullptr;
+    int32_t* link_deg = nullptr;
+    size_t link_cap = 0;  // rows staged at most
+    int link_stride = 0;
+    unsigned long long* link_cnt = nullptr;
+    int64_t link_rows = 0, link_edges = 0;
+    double link_us = 0;
     // shape
     int dim = 0, pitch = 0, lpr = 0, vpl = 0;
     bool layers_exist = false;

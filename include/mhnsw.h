@@ -76,7 +76,19 @@ int mhnsw_seed(mhnsw_index *h, uint64_t seed); /* Rng = rand.New(rand.NewSource(
  * % of the rows already indexed, default 5 -- a batch is searched against the index as it
  * stood before it, so larger batches build faster but link a batch's rows to each other
  * only through reverse edges: adding 1,000 rows to a 5,100-row index in one 20 % batch
- * left 16 % of them unreachable by their own vector at ef 64), "vis_log2" (compat / build visited sets:
+ * left 16 % of them unreachable by their own vector at ef 64; "batch_link" 1 is the remedy),
+ * "batch_link" (batched insert, 0 (default) or 1: after a layer's commit every row of the
+ * batch searches the layer again, now that its batch-mates are in it, and takes the
+ * batch-mates it finds into its neighbour selection -- the build rate with and without it
+ * is measured in profiles/batch_link.txt; batch mode only, the compat and flat builds
+ * ignore it),
+ * "batch_link_ef" (the width of that search: 0 (default) = the width of the layer's insert
+ * search, else clamped to [the layer's degree cap, 512]); read-only, of the last Add:
+ * "last_link_rows" (rows, one per layer, whose selection the link pass changed),
+ * "last_link_edges" (the batch-mates those selections added, counted as selected: the
+ * commit's overflow rule may prune one again, and the reverse edges the proposals add are
+ * not counted), "last_link_ns" (its kernels' device time with
+ * "time_build" 1, else 0), "vis_log2" (compat / build visited sets:
  * 2^n entries), "vis_entries" (beam search's visited set, 0 = 1.25 * 2^vis_log2),
  * "build_expand" (batched insert: entries expanded per step of its layer
  * searches, 1-4, default 4 -- they fetch their adjacency rows in one round
