@@ -350,22 +350,31 @@ int run_build_compat(mhnsw_index* h, int64_t n0, int64_t n1, int top0, const int
 // batch sorted by level); otherwise every layer's launch covers the whole
 // batch and descends the others itself.  Both read each layer before its
 // commit, so they build the same graph.
-int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t entry) {
+//
+// rows (nullable, a host list): the row-list form, mhnsw_update's re-insert -- the batch is the
+// stored rows rows[a0 .. a1) at their existing ids and levels (members of their layers with
+// empty rows), not the ids [a0, a1).  The level-sorted list then always goes to the device: it
+// is what the kernels read the ids from (BatchBuildArgs::rows).  No link pass (update.hip).
+int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t entry, const uint32_t* rows) {
     if (a1 <= a0) return 0;
-    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(h->cur_entry + a0), (int)entry, (size_t)(a1 - a0), h->stream));
+    auto row_of = [&](int64_t i) -> int64_t { return rows ? (int64_t)rows[i] : i; };
+    if (rows)  // (every row's word: 4 bytes per stored row, nothing next to the detach's passes)
+        HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->cur_entry, (int)entry, (size_t)h->n, h->stream));
+    else
+        HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(h->cur_entry + a0), (int)entry, (size_t)(a1 - a0), h->stream));
     int maxlvl = 0;
-    for (int64_t i = a0; i < a1; ++i) maxlvl = std::max(maxlvl, h->hlevels[i]);
+    for (int64_t i = a0; i < a1; ++i) maxlvl = std::max(maxlvl, h->hlevels[row_of(i)]);
     int r;
     if ((r = sync_layer_table(h))) return r;
     const int efc = h->efc > 0 ? h->efc : h->ef;
     const int64_t nb = a1 - a0;
     std::vector<int64_t> count(MH_MAXL + 1, 0);  // nodes with level >= l
-    for (int64_t i = a0; i < a1; ++i) count[std::min(h->hlevels[i], MH_MAXL)]++;
+    for (int64_t i = a0; i < a1; ++i) count[std::min(h->hlevels[row_of(i)], MH_MAXL)]++;
     for (int l = MH_MAXL - 1; l >= 0; --l) count[l] += count[l + 1];
     const bool fuse = h->fuse_descent != 0;
     // batch_link: the layers whose launch covers at least two batch rows get the link pass
-    const bool link = h->batch_link != 0 && nb >= 2;
-    if (fuse) {
+    const bool link = h->batch_link != 0 && nb >= 2 && !rows;
+    if (fuse || rows) {
         if (h->ord_cap < nb) {
             if (h->ord_pin) (void)hipHostFree(h->ord_pin);
             h->ord_pin = nullptr;
@@ -378,7 +387,8 @@ int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t e
         if (h->ord_pending) HIPCHK(h, hipEventSynchronize(h->ord_ev));  // the previous batch's copy has read ord_pin
         std::vector<int64_t> pos(MH_MAXL + 1, 0);  // level-descending, stable within a level
         for (int l = 0; l <= MH_MAXL; ++l) pos[l] = l < MH_MAXL ? count[l + 1] : 0;
-        for (int64_t i = a0; i < a1; ++i) h->ord_pin[pos[std::min(h->hlevels[i], MH_MAXL)]++] = (uint32_t)i;
+        for (int64_t i = a0; i < a1; ++i)
+            h->ord_pin[pos[std::min(h->hlevels[row_of(i)], MH_MAXL)]++] = (uint32_t)row_of(i);
         HIPCHK(h, hipMemcpyAsync(h->border.p, h->ord_pin, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipEventRecord(h->ord_ev, h->stream));
         h->ord_pending = true;
@@ -398,8 +408,9 @@ int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t e
         a.count = 0;
         a.g = graph_view(h);
         a.layer = l;
-        a.n0 = a0;
-        a.n1 = a1;
+        a.n0 = rows ? 0 : a0;
+        a.n1 = rows ? nb : a1;
+        a.rows = rows ? h->border.p : nullptr;
         a.levels = h->levels;
         a.cur_entry = h->cur_entry;
         // upper_efc: a narrower candidate list in the layers above 0 (their rows hold M,
@@ -488,11 +499,9 @@ int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t e
     return 0;
 }
 
-// top / entry: the live top layer and its entry before this batch (-1: empty graph)
-int run_build_batch(mhnsw_index* h, int64_t n0, int64_t n1, int top, uint32_t entry,
-                    const std::function<void()>& while_gpu) {
+// the reverse proposals' slots and the touched list of a batch of at most batch_max inserts
+int ensure_batch_scratch(mhnsw_index* h) {
     int r;
-    if ((r = zero_err(h))) return r;
     if (!h->inc_src) {
         if ((r = grow(h, h->inc_src, 0, h->capn * h->inc_cap, 0))) return r;
         if ((r = grow(h, h->inc_dist, 0, h->capn * h->inc_cap, 0))) return r;
@@ -500,9 +509,37 @@ int run_build_batch(mhnsw_index* h, int64_t n0, int64_t n1, int top, uint32_t en
     const size_t tneed = (size_t)h->batch_max * (size_t)std::max(m0_of(h), h->M) + 64;
     if (h->touched_cap < tneed) {
         if (h->touched) (void)hipFree(h->touched);
+        h->touched = nullptr;
+        h->touched_cap = 0;
         if (hipMalloc(&h->touched, tneed * 4) != hipSuccess) return fail(h, MHNSW_ENOMEM, "device allocation failed");
         h->touched_cap = tneed;
     }
+    return 0;
+}
+
+// the device time between the event pairs that run_batch_layers recorded (option time_build)
+int collect_build_times(mhnsw_index* h) {
+    for (size_t i = 0; i + 1 < h->tev_used; i += 2) {
+        float ms = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->tev[i], h->tev[i + 1]));
+        h->build_search_us += ms * 1e3;
+    }
+    h->tev_used = 0;
+    for (size_t i = 0; i + 1 < h->ltev_used; i += 2) {
+        float ms = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ltev[i], h->ltev[i + 1]));
+        h->build_search_us += ms * 1e3;
+        h->link_us += ms * 1e3;
+    }
+    h->ltev_used = 0;
+    return 0;
+}
+
+// top / entry: the live top layer and its entry before this batch (-1: empty graph)
+int run_build_batch(mhnsw_index* h, int64_t n0, int64_t n1, int top, uint32_t entry,
+                    const std::function<void()>& while_gpu) {
+    int r;
+    if ((r = zero_err(h)) || (r = ensure_batch_scratch(h))) return r;
     if (h->batch_link) {  // the link pass's staging rows, grown like `touched`, and its counters
         int stride = std::max(cap_of(h, 0), cap_of(h, 1));
         for (const Layer& L : h->layers) stride = std::max(stride, L.cap);
@@ -1074,19 +1111,7 @@ int add_step(mhnsw_index* h, const int64_t* keys, const float* vecs, bool vecs_o
         publish_keys();  // (an early device error: the rows exist, so do their keys)
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (size_t i = 0; i + 1 < h->tev_used; i += 2) {
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->tev[i], h->tev[i + 1]));
-        h->build_search_us += ms * 1e3;
-    }
-    h->tev_used = 0;
-    for (size_t i = 0; i + 1 < h->ltev_used; i += 2) {
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, h->ltev[i], h->ltev[i + 1]));
-        h->build_search_us += ms * 1e3;
-        h->link_us += ms * 1e3;
-    }
-    h->ltev_used = 0;
+    if (int rt = collect_build_times(h)) return rt;
     if (r == 0) *reached = nproc;
     *cont_out = cont;
     return r;
@@ -1261,6 +1286,9 @@ void mhnsw_destroy(mhnsw_index* h) {
     F(h->rstat.p);
     F(h->rlims.p);
     F(h->rkeys.p);
+    F(h->uids.p);
+    F(h->d_repaired);
+    for (auto e : h->uev) (void)hipEventDestroy(e);
     for (auto e : h->fxev)
         if (e) (void)hipEventDestroy(e);
     if (h->scr_ev) (void)hipEventDestroy(h->scr_ev);
@@ -1542,6 +1570,15 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
         if (!h->have_compact_timing || hipEventElapsedTime(&ms, h->cev0, h->cev1) != hipSuccess) return MHNSW_EINVAL;
         *v = (int64_t)std::llround((double)ms * 1e6);
     }
+    // read-only, of the last mhnsw_update: rows updated, chunks, (layer, row) pairs whose adjacency the
+    // detach rebuilt, and the device time (time_build; else 0) of the call and of its three steps
+    else if (n == "last_update_rows") *v = h->update_rows;
+    else if (n == "last_update_chunks") *v = h->update_chunks;
+    else if (n == "last_update_repaired") *v = h->update_repaired;
+    else if (n == "last_update_ns") *v = (int64_t)std::llround((h->update_us[0] + h->update_us[1] + h->update_us[2]) * 1e3);
+    else if (n == "last_update_detach_ns") *v = (int64_t)std::llround(h->update_us[0] * 1e3);
+    else if (n == "last_update_overwrite_ns") *v = (int64_t)std::llround(h->update_us[1] * 1e3);
+    else if (n == "last_update_insert_ns") *v = (int64_t)std::llround(h->update_us[2] * 1e3);
     else if (n == "range_expect") *v = h->range_expect;
     else if (n == "range_force_fallback") *v = h->range_force_fallback;
     else if (n == "last_range_candidates" || n == "last_range_fallback_queries") {
@@ -1984,6 +2021,212 @@ int mhnsw_replace(mhnsw_index* h, const int64_t* keys, const float* vecs, int64_
                                 h->stream));
     h->xsplit_rows = std::min(h->xsplit_rows, lo);
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+}  // extern "C"
+
+// Update: new vectors for present keys, in place (include/mhnsw.h; the device steps: update.hip).
+// Rows keep their ids, levels, layer membership and filter bits; the host mirrors (key map,
+// hdead, hmask, layer counts and entries) and the Rng are not written at all.
+static int update_impl(mhnsw_index* h, const int64_t* keys, const float* vecs, bool on_device, int64_t n, int dim,
+                       uint8_t* out_found) {
+    if (n > 0 && (!keys || !vecs || !out_found))
+        return fail(h, MHNSW_EINVAL, "keys, vecs and out_found must be non-NULL");
+    if (h->build_mode == MHNSW_BUILD_COMPAT || h->aliased || h->partial_rows > 0)
+        return fail(h, MHNSW_EUNSUPPORTED, "update needs a batch or flat (build_mode 1 or 2) handle");
+    if (n <= 0) return MHNSW_OK;
+    if (h->layers_exist && dim != h->dim)
+        return fail(h, MHNSW_EDIM, "embedding dimension mismatch: %d != %d", h->dim, dim);
+    {
+        std::unordered_set<int64_t> seen;
+        seen.reserve((size_t)n);
+        for (int64_t i = 0; i < n; ++i)
+            if (!seen.insert(keys[i]).second)
+                return fail(h, MHNSW_EINVAL, "duplicate key %lld in update", (long long)keys[i]);
+    }
+    h->update_rows = h->update_chunks = h->update_repaired = 0;
+    h->update_us[0] = h->update_us[1] = h->update_us[2] = 0;
+    std::vector<uint32_t> ids, from;  // the found keys' rows, and their positions in the call
+    for (int64_t i = 0; i < n; ++i) {
+        out_found[i] = 0;
+        auto it = h->key2id.find(keys[i]);
+        if (it == h->key2id.end() || h->hdead[it->second] || !in_layer(h, it->second, 0)) continue;
+        out_found[i] = 1;
+        ids.push_back((uint32_t)it->second);
+        from.push_back((uint32_t)i);
+    }
+    const int64_t m = (int64_t)ids.size();
+    if (m == 0) return MHNSW_OK;
+    ++h->mut_epoch;
+    const bool flat = h->build_mode == MHNSW_BUILD_FLAT;
+    hipStream_t s = h->stream;
+    int r;
+    if ((r = zero_err(h)) || (r = sync_layer_table(h))) return r;
+    if (!flat && (r = ensure_batch_scratch(h))) return r;
+    // staging: the call's vectors (a host call's go through tmp), all n padded, the id lists
+    const size_t raw = on_device ? 0 : ((size_t)n * dim + 3) / 4 * 4;  // (the padded rows stay 16-byte aligned)
+    if ((r = ensure_buf(h, h->tmp, raw + (size_t)n * h->pitch)) || (r = ensure_buf(h, h->uids, 2 * (size_t)m))) return r;
+    if (!h->d_repaired && hipMalloc(&h->d_repaired, sizeof(unsigned long long)) != hipSuccess)
+        return fail(h, MHNSW_ENOMEM, "device allocation failed");
+    const float* src = vecs;
+    if (!on_device) {
+        HIPCHK(h, hipMemcpyAsync(h->tmp.p, vecs, (size_t)n * dim * 4, hipMemcpyHostToDevice, s));
+        src = h->tmp.p;
+    }
+    float* padded = h->tmp.p + raw;
+    uint32_t* d_ids = h->uids.p;
+    uint32_t* d_from = h->uids.p + m;
+    LCHK(h, launch_pad_rows(src, n, dim, padded, h->pitch, s));
+    HIPCHK(h, hipMemcpyAsync(d_ids, ids.data(), (size_t)m * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d_from, from.data(), (size_t)m * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemsetAsync(h->d_repaired, 0, sizeof(unsigned long long), s));
+    // A chunk is bounded like a batch of Add (its rows are re-inserted against the graph without
+    // them), and by half of the live rows: the graph a chunk is re-inserted into is never empty.
+    const int64_t live = live_count(h);
+    int64_t bsz = std::max<int64_t>(h->batch_min, (int64_t)((double)live * h->batch_ratio_pct / 100.0));
+    bsz = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(bsz, h->batch_max), live / 2));
+    if (flat) bsz = m;
+    size_t nev = 0;
+    auto mark = [&]() -> int {  // time_build: an event between the steps
+        if (!h->time_build) return 0;
+        if (nev == h->uev.size()) {
+            hipEvent_t e;
+            HIPCHK(h, hipEventCreate(&e));
+            h->uev.push_back(e);
+        }
+        HIPCHK(h, hipEventRecord(h->uev[nev++], s));
+        return 0;
+    };
+    std::vector<uint8_t> in_u(flat ? 0 : (size_t)h->n, 0);
+    const int nl = (int)h->layers.size();
+    for (int64_t c0 = 0; c0 < m; c0 += bsz) {
+        const int64_t cnt = std::min(bsz, m - c0);
+        ++h->update_chunks;
+        if ((r = mark())) return r;
+        if (!flat) {
+            // detach: the chunk's rows marked, every live row that points at one rebuilt (the Delete
+            // path's repair, over the old vectors), their own rows emptied, the marks cleared
+            LCHK(h, launch_update_mark(h->dead, d_ids + c0, cnt, UPDATE_MARK, s));
+            DeleteArgs a;
+            memset(&a, 0, sizeof(a));
+            a.g = graph_view(h);
+            a.g.dead = h->dead;
+            a.stats = h->d_stats + 4;
+            a.err = h->d_err;
+            a.vis_log2 = h->vis_log2;
+            a.n = h->n;
+            a.heuristic = h->heuristic;
+            a.keep_pruned = h->keep_pruned;
+            a.repaired = h->d_repaired;
+            for (int l = 0; l < nl; ++l) {
+                a.layer = l;
+                a.mcap = l == 0 ? m0_of(h) : h->M;
+                LCHK(h, launch_delete_repair(a, h->lpr, h->vpl, s));
+            }
+            for (auto& L : h->layers) LCHK(h, launch_update_detach(L.deg, L.adj, L.adjd, L.cap, h->n, h->dead, s));
+            LCHK(h, launch_update_mark(h->dead, d_ids + c0, cnt, 0, s));
+        }
+        if ((r = mark())) return r;
+        // overwrite: vectors, norms, the screening copy and the exact path's planes, by row list
+        LCHK(h, launch_update_scatter(padded, d_ids + c0, d_from + c0, cnt, h->pitch, h->vecs, s));
+        LCHK(h, launch_norms_ids(h->vecs, d_ids + c0, cnt, h->pitch, h->lpr, h->vpl, h->norms, s));
+        if (h->screen & 1 && h->h16 && h->h16_metric == h->metric)
+            LCHK(h, launch_h16_rows_ids(h->vecs, h->norms, d_ids + c0, cnt, h->pitch, h->metric, h->h16, h->h16aux,
+                                        h->h16err, s));
+        // (planes converted so far, in a buffer of the current capacity: rows past xsplit_rows are
+        // written to the values the next exact search gives them anyway; an unconverted or
+        // outgrown buffer is rebuilt by that search)
+        if (h->xsplit_rows > 0 && h->xsplit.p && h->xsplit_plane == h->capn * h->pitch &&
+            h->xsplit.n >= (size_t)h->xsplit_plane * 2) {
+            uint16_t* xh = h->xsplit.p;
+            if (h->xsplit_kind == 2 && h->xinv.n >= (size_t)h->capn && h->xerr.p)
+                LCHK(h, launch_split_h16_ids(h->vecs, d_ids + c0, cnt, h->pitch, h->capn, xh, nullptr, h->xinv.p,
+                                             h->xerr.p, s));
+            else if (h->xsplit_kind == 1)
+                LCHK(h, launch_split_rows_ids(h->vecs, d_ids + c0, cnt, h->pitch, h->capn, xh,
+                                              xh + (size_t)h->capn * h->pitch, s));
+            else
+                h->xsplit_rows = 0;
+        }
+        if ((r = mark())) return r;
+        if (!flat) {
+            // re-insert from an entry outside the chunk: the highest layer with such a member, and
+            // there the layer's entry, else its lowest-id live member (fix_entries' choice)
+            std::vector<int64_t> in_chunk((size_t)nl, 0);
+            for (int64_t j = c0; j < c0 + cnt; ++j) {
+                in_u[ids[j]] = 1;
+                for (int l = 0; l < nl; ++l) in_chunk[l] += in_layer(h, ids[j], l);
+            }
+            int top = top_live_layer(h);
+            while (top >= 0 && h->layers[top].count - in_chunk[top] <= 0) --top;
+            int64_t entry = -1;
+            if (top >= 0) {
+                const Layer& L = h->layers[top];
+                if (L.entry >= 0 && in_layer(h, L.entry, top) && !h->hdead[L.entry] && !in_u[L.entry]) entry = L.entry;
+                for (int64_t i = 0; i < h->n && entry < 0; ++i)
+                    if (in_layer(h, i, top) && !h->hdead[i] && !in_u[i]) entry = i;
+            }
+            for (int64_t j = c0; j < c0 + cnt; ++j) in_u[ids[j]] = 0;
+            // (no such layer: the chunk is every live row -- one row, by the bound above -- and
+            // has nothing to link to)
+            if (entry >= 0 && (r = run_batch_layers(h, c0, c0 + cnt, top, (uint32_t)entry, ids.data()))) return r;
+        }
+        if ((r = mark())) return r;
+    }
+    int err = 0;
+    unsigned long long rep = 0;
+    HIPCHK(h, hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(&rep, h->d_repaired, sizeof(rep), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if ((r = collect_build_times(h))) return r;
+    for (size_t c = 0; c + 3 < nev; c += 4)
+        for (int k = 0; k < 3; ++k) {
+            float ms = 0.f;
+            HIPCHK(h, hipEventElapsedTime(&ms, h->uev[c + k], h->uev[c + k + 1]));
+            h->update_us[k] += ms * 1e3;
+        }
+    h->update_rows = m;
+    h->update_repaired = (int64_t)rep;
+    if (err & 4) return fail(h, MHNSW_EINTERNAL, "out-of-range node id in adjacency (graph corrupt)");
+    return MHNSW_OK;
+}
+
+extern "C" {
+
+int mhnsw_update(mhnsw_index* h, const int64_t* keys, const float* vecs, int64_t n, int dim, uint8_t* out_found) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    if (int r0 = drain(h)) return r0;
+    return update_impl(h, keys, vecs, false, n, dim, out_found);
+}
+
+int mhnsw_update_device(mhnsw_index* h, const int64_t* keys, const float* d_vecs, int64_t n, int dim,
+                        uint8_t* out_found) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    HIPCHK(h, hipDeviceSynchronize());  // order after whatever produced d_vecs (and any enqueued search)
+    h->scr_valid = false;
+    return update_impl(h, keys, d_vecs, true, n, dim, out_found);
+}
+
+int mhnsw_export_edge_dist(mhnsw_index* h, float* adjd, int cap) {
+    std::shared_lock<std::shared_mutex> lk(h->mu);
+    const int64_t N = h->n;
+    if (N == 0) return 0;
+    if (!adjd) return fail(h, MHNSW_EINVAL, "adjd must be non-NULL");
+    std::vector<int32_t> deg((size_t)N);
+    std::vector<float> row;
+    for (int l = 0; l < (int)h->layers.size(); ++l) {
+        const Layer& L = h->layers[l];
+        HIPCHK(h, hipMemcpy(deg.data(), L.deg, N * 4, hipMemcpyDeviceToHost));
+        row.resize((size_t)N * L.cap);
+        HIPCHK(h, hipMemcpy(row.data(), L.adjd, (size_t)N * L.cap * 4, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < N; ++i) {
+            const int d = deg[i];
+            if (d > cap) return fail(h, MHNSW_EINVAL, "export cap %d smaller than degree %d", cap, d);
+            float* o = adjd + ((size_t)l * N + i) * cap;
+            for (int j = 0; j < cap; ++j) o[j] = (j < d) ? row[(size_t)i * L.cap + j] : 0.f;
+        }
+    }
     return 0;
 }
 

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(64) void k_batch_descend(BatchBuildArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int64_t u64 = a.n0 + blockIdx.x;
     if (u64 >= a.n1) return;
-    const uint32_t u = (uint32_t)u64;
+    const uint32_t u = a.rows ? a.rows[u64] : (uint32_t)u64;  // (the row-list form: BatchBuildArgs::rows)
     const int lv = a.levels[u];
     if (lv >= a.layer) return;
     WaveStats st;
@@ -322,7 +322,7 @@ __device__ __forceinline__ bool batch_node(const BatchBuildArgs& a, uint32_t& u)
     } else {
         const int64_t u64 = a.n0 + blockIdx.x;
         if (u64 >= a.n1) return false;
-        u = (uint32_t)u64;
+        u = a.rows ? a.rows[u64] : (uint32_t)u64;
     }
     return true;
 }
@@ -643,6 +643,7 @@ __global__ __launch_bounds__(64) void k_delete_repair(DeleteArgs a) {
     if (lane == 0) {
         a.g.layers[l].deg[v] = nkeep;
         atomicAdd(&a.stats[0], st.E);
+        if (a.repaired) atomicAdd(a.repaired, 1ull);
     }
 }
 

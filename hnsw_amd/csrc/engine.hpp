@@ -151,6 +151,11 @@ int launch_scatter_rows(const float* src, const int32_t* ids, int64_t n, int pit
 int launch_h16_rows(const float* X, const float* norms, int64_t n0, int64_t n1, int pitch, int metric, uint16_t* H,
                     float2* aux, float* err, hipStream_t s);
 int launch_norms(const float* X, int64_t n0, int64_t n1, int pitch, int lpr, int vpl, float* out, hipStream_t s);
+// the same kernels over a list of rows, ids[0 .. m) (the in-place update: work proportional to m)
+int launch_norms_ids(const float* X, const uint32_t* ids, int64_t m, int pitch, int lpr, int vpl, float* out,
+                     hipStream_t s);
+int launch_h16_rows_ids(const float* X, const float* norms, const uint32_t* ids, int64_t m, int pitch, int metric,
+                        uint16_t* H, float2* aux, float* err, hipStream_t s);
 int launch_sweep(const float* q, const float* X, int64_t n, int pitch, int lpr, int vpl, int metric, float* out,
                  hipStream_t s);
 int launch_sweep_raw(const float* q, const float* X, int64_t n, int dim, int metric, float* out, hipStream_t s);
@@ -200,6 +205,7 @@ struct DeleteArgs {
     unsigned long long* stats;    // [0]=dist evals
     int* err;
     int vis_log2;
+    unsigned long long* repaired;  // repair (nullable): += rows rebuilt (the in-place update's detach counts them)
 };
 constexpr int REPAIR_POOL = 256;  // candidate pool per repaired row (oracle: OG_REPAIR_POOL)
 int launch_delete_compat(const DeleteArgs& a, int lpr, int vpl, hipStream_t s);
@@ -229,6 +235,10 @@ struct BatchBuildArgs {
     int64_t count;                //   level descending so that level >= layer is a prefix
     int64_t mw_max = 0;           // launches of at most this many inserts: one workgroup of 4 waves per insert
     int vis16 = 0;                // the layer searches' visited set is the compact 16-bit one (ids < 2^24)
+    // The row-list form (nullable; the in-place update, update.hip): the batch is rows[n0 .. n1),
+    // stored rows at their existing ids and levels, instead of the ids [n0, n1) themselves.
+    // `order` holds row ids either way; cur_entry, inc_* and levels are indexed by row id.
+    const uint32_t* rows = nullptr;
 };
 int launch_build_batch_search(const BatchBuildArgs& a, int lpr, int vpl, hipStream_t s);
 // greedy descent of every node u in [n0, n1) through layers a.layer .. levels[u] + 1
@@ -322,6 +332,11 @@ int launch_split_h16(const float* src, int64_t r0, int64_t r1, int pitch, int64_
 int launch_exact_select(const ExactArgs& a, hipStream_t s);
 int launch_split_rows(const float* src, int64_t r0, int64_t r1, int pitch, int64_t rows, uint16_t* hi, uint16_t* lo,
                       hipStream_t s);
+// the planes of rows ids[0 .. m), each below `rows` (the in-place update)
+int launch_split_rows_ids(const float* src, const uint32_t* ids, int64_t m, int pitch, int64_t rows, uint16_t* hi,
+                          uint16_t* lo, hipStream_t s);
+int launch_split_h16_ids(const float* src, const uint32_t* ids, int64_t m, int pitch, int64_t rows, uint16_t* hi,
+                         uint16_t* lo, float* inv, float* err, hipStream_t s);
 int launch_max_norm(const float* norms, int64_t n, float* out, hipStream_t s);
 
 // ---- filtered exact search: the allowed rows as a dense row set (rowset.hip) ----
@@ -357,6 +372,19 @@ int launch_compact_adj(int32_t* deg, int32_t* adj, float* adjd, int cap, int64_t
                        int64_t n_old, unsigned long long* dangling, hipStream_t s);
 // out bit j = old bit src[j] for j < live, 0 above; nwords words each, out != old
 int launch_compact_filter(const uint32_t* old, uint32_t* out, int64_t nwords, const uint32_t* src, int64_t live,
+                          hipStream_t s);
+
+// ---- update: stored rows re-embedded in place (update.hip) ----
+// dead[ids[j]] = v for j < m: the chunk's rows are marked (UPDATE_MARK) while the delete repair
+// detaches them, and unmarked (0) afterwards
+constexpr uint8_t UPDATE_MARK = 2;  // a `dead` byte that is neither live (0) nor deleted (1)
+int launch_update_mark(uint8_t* dead, const uint32_t* ids, int64_t m, uint8_t v, hipStream_t s);
+// rows [0, rows) of a layer: a marked member loses its row (deg 0, adj -1, adjd 0); a deleted
+// row drops its edges to marked rows (row order kept, as launch_compact_adj closes a row up)
+int launch_update_detach(int32_t* deg, int32_t* adj, float* adjd, int cap, int64_t rows, const uint8_t* dead,
+                         hipStream_t s);
+// src row from[j] (padded) -> dst row ids[j] for j < m, in whole 16-byte words
+int launch_update_scatter(const float* src, const uint32_t* ids, const uint32_t* from, int64_t m, int pitch, float* dst,
                           hipStream_t s);
 
 // certificate of the re-rank (nullable pieces disable it)

@@ -155,13 +155,15 @@ __device__ __forceinline__ float bf16_val(uint32_t h) { return __uint_as_float(h
 // x = hi + lo + r with hi = bf16(x), lo = bf16(x - hi) (x - hi is exact in f32),
 // |r| <= 2^-16 |x|.  Rows [r0, r1) of a pitch-strided f32 array go to K-blocked
 // planes: element (row, k) at ((k / 16) * rows + row) * 16 + k % 16, so one GEMM
-// K-stage of consecutive rows is a single contiguous run.
+// K-stage of consecutive rows is a single contiguous run.  ids (nullable): position j of
+// [r0, r1) stands for row ids[j] (the in-place update's row list), else for row j.
 __global__ void k_split_rows(const float* __restrict__ src, int64_t r0, int64_t r1, int pitch, int64_t rows,
-                             uint16_t* __restrict__ hi, uint16_t* __restrict__ lo) {
+                             uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, const uint32_t* __restrict__ ids) {
     const int q4 = pitch / 4;
     const int64_t total = (r1 - r0) * (int64_t)q4;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t row = r0 + i / q4;
+        const int64_t pos = r0 + i / q4;
+        const int64_t row = ids ? (int64_t)ids[pos] : pos;
         const int k = (int)(i % q4) * 4;
         const float4 v = *reinterpret_cast<const float4*>(src + row * (int64_t)pitch + k);
         const uint32_t a0 = bf16_rne(v.x), a1 = bf16_rne(v.y), a2 = bf16_rne(v.z), a3 = bf16_rne(v.w);
@@ -179,7 +181,19 @@ int launch_split_rows(const float* src, int64_t r0, int64_t r1, int pitch, int64
     if (pitch % X3K || r1 > rows) return -5;
     const int64_t total = (r1 - r0) * (int64_t)pitch / 4;
     const int grid = (int)std::min<int64_t>((total + 255) / 256, 8192);
-    hipLaunchKernelGGL(k_split_rows, dim3(grid), dim3(256), 0, s, src, r0, r1, pitch, rows, hi, lo);
+    hipLaunchKernelGGL(k_split_rows, dim3(grid), dim3(256), 0, s, src, r0, r1, pitch, rows, hi, lo,
+                       (const uint32_t*)nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// rows ids[0 .. m), each below `rows` (the caller's list)
+int launch_split_rows_ids(const float* src, const uint32_t* ids, int64_t m, int pitch, int64_t rows, uint16_t* hi,
+                          uint16_t* lo, hipStream_t s) {
+    if (m <= 0) return 0;
+    if (pitch % X3K) return -5;
+    const int64_t total = m * (int64_t)pitch / 4;
+    const int grid = (int)std::min<int64_t>((total + 255) / 256, 8192);
+    hipLaunchKernelGGL(k_split_rows, dim3(grid), dim3(256), 0, s, src, (int64_t)0, m, pitch, rows, hi, lo, ids);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -194,10 +208,12 @@ int launch_split_rows(const float* src, int64_t r0, int64_t r1, int pitch, int64
 // wave per row.
 __global__ __launch_bounds__(256) void k_split_h16(const float* __restrict__ src, int64_t r0, int64_t r1, int pitch,
                                                    int64_t rows, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo,
-                                                   float* __restrict__ inv, float* __restrict__ err) {
+                                                   float* __restrict__ inv, float* __restrict__ err,
+                                                   const uint32_t* __restrict__ ids) {
     const int lane = threadIdx.x & 63;
-    const int64_t row = r0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= r1) return;
+    const int64_t pos = r0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pos >= r1) return;
+    const int64_t row = ids ? (int64_t)ids[pos] : pos;  // (ids: as k_split_rows)
     const float* xp = src + row * (int64_t)pitch;
     float m = 0.f;
     bool fin = true;
@@ -252,7 +268,16 @@ int launch_split_h16(const float* src, int64_t r0, int64_t r1, int pitch, int64_
     if (r1 <= r0) return 0;
     if (pitch % X3K || r1 > rows) return -5;
     hipLaunchKernelGGL(k_split_h16, dim3((unsigned)((r1 - r0 + 3) / 4)), dim3(256), 0, s, src, r0, r1, pitch, rows, hi,
-                       lo, inv, err);
+                       lo, inv, err, (const uint32_t*)nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_split_h16_ids(const float* src, const uint32_t* ids, int64_t m, int pitch, int64_t rows, uint16_t* hi,
+                         uint16_t* lo, float* inv, float* err, hipStream_t s) {
+    if (m <= 0) return 0;
+    if (pitch % X3K) return -5;
+    hipLaunchKernelGGL(k_split_h16, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s, src, (int64_t)0, m, pitch, rows, hi,
+                       lo, inv, err, ids);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -271,6 +271,14 @@ struct mhnsw_index {
     hipEvent_t cev0 = nullptr, cev1 = nullptr;
     bool have_compact_timing = false;
     int64_t compact_scratch_bytes = 0, compact_dangling = 0;
+    // in-place update (mhnsw_update): of the last call the rows updated, its chunks, the (layer, row)
+    // pairs the detach rebuilt and, with time_build, the device time of its three steps (detach,
+    // overwrite, re-insert); the id list and repair counter on the device, the steps' events
+    int64_t update_rows = 0, update_chunks = 0, update_repaired = 0;
+    double update_us[3] = {0, 0, 0};
+    DevBuf<uint32_t> uids;
+    unsigned long long* d_repaired = nullptr;
+    std::vector<hipEvent_t> uev;
     std::string err;
     mutable std::shared_mutex mu;
 };
@@ -311,7 +319,9 @@ int set_shape(mhnsw_index* h, int dim);
 int set_deg(mhnsw_index* h, int l, int64_t id, int32_t v);
 int sync_layer_entries(mhnsw_index* h);
 int zero_err(mhnsw_index* h);
-int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t entry);
+int run_batch_layers(mhnsw_index* h, int64_t a0, int64_t a1, int top, uint32_t entry, const uint32_t* rows = nullptr);
+int ensure_batch_scratch(mhnsw_index* h);
+int collect_build_times(mhnsw_index* h);
 int run_build_batch(mhnsw_index* h, int64_t n0, int64_t n1, int top, uint32_t entry,
                     const std::function<void()>& while_gpu = nullptr);
 int h16_rows(mhnsw_index* h, int64_t r0, int64_t r1);

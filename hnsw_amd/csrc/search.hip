@@ -64,17 +64,20 @@ int launch_scatter_rows(const float* src, const int32_t* ids, int64_t n, int pit
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// canonical |x| per row: one wave handles RPI rows per step
+// canonical |x| per row: one wave handles RPI rows per step.  ids (nullable): position j of
+// [n0, n1) stands for row ids[j] (the in-place update's row list), else for row j.
 template <class C>
 __global__ __launch_bounds__(256) void k_norms(const float* __restrict__ X, int64_t n0, int64_t n1, int pitch,
-                                               float* __restrict__ out) {
+                                               float* __restrict__ out, const uint32_t* __restrict__ ids) {
     const int lane = lane_id();
     const int wave = threadIdx.x >> 6;
     const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
-    const int64_t row = n0 + gw * C::RPI + lane / C::LPR;
+    const int64_t pos = n0 + gw * C::RPI + lane / C::LPR;
+    const bool in = pos < n1;
+    const int64_t row = ids && in ? (int64_t)ids[pos] : pos;
     const int sub = lane & (C::LPR - 1);
     float acc = 0.f;
-    if (row < n1) {
+    if (in) {
         const float* rp = X + (size_t)row * pitch + sub * 4;
 #pragma unroll
         for (int v = 0; v < C::VPL; ++v) {
@@ -86,7 +89,7 @@ __global__ __launch_bounds__(256) void k_norms(const float* __restrict__ X, int6
         }
     }
     acc = seg_allreduce<C::LPR>(acc);
-    if (row < n1 && sub == 0) out[row] = sqrtf(acc);
+    if (in && sub == 0) out[row] = sqrtf(acc);
 }
 
 // distance of one query against n rows (mhnsw_distance)
@@ -290,12 +293,13 @@ int launch_sweep_raw(const float* q, const float* X, int64_t n, int dim, int met
 }
 
 template <class C>
-static int launch_norms_t(const float* X, int64_t n0, int64_t n1, int pitch, float* out, hipStream_t s) {
+static int launch_norms_t(const float* X, int64_t n0, int64_t n1, int pitch, float* out, hipStream_t s,
+                          const uint32_t* ids = nullptr) {
     const int64_t rows = n1 - n0;
     if (rows <= 0) return 0;
     const int64_t waves = (rows + C::RPI - 1) / C::RPI;
     const int grid = (int)((waves + 3) / 4);
-    hipLaunchKernelGGL(k_norms<C>, dim3(grid), dim3(256), 0, s, X, n0, n1, pitch, out);
+    hipLaunchKernelGGL(k_norms<C>, dim3(grid), dim3(256), 0, s, X, n0, n1, pitch, out, ids);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -312,7 +316,8 @@ static int launch_sweep_t(const float* q, const float* X, int64_t n, int pitch, 
 
 // ---------------------------------------------------------------------------
 // fp16 screening copy of rows [n0, n1) (device_common.hpp GraphDev::h16), one
-// wave per row; norms[r] (canonical |x|) must already be written.
+// wave per row; norms[r] (canonical |x|) must already be written.  ids (nullable):
+// position j of [n0, n1) stands for row ids[j], else for row j.
 //   cosine: fp16(x_i * (1/|x|) * 2^14); rows outside the screen's validity
 //           range (max|x_i| not in [2^-50, 2^50], any non-finite value) get
 //           NaN halves, which make every screening test on them false
@@ -323,10 +328,11 @@ static int launch_sweep_t(const float* q, const float* X, int64_t n, int pitch, 
 __global__ __launch_bounds__(256) void k_h16_rows(const float* __restrict__ X, const float* __restrict__ norms,
                                                   int64_t n0, int64_t n1, int pitch, int metric,
                                                   uint16_t* __restrict__ H, float2* __restrict__ aux,
-                                                  float* __restrict__ err) {
+                                                  float* __restrict__ err, const uint32_t* __restrict__ ids) {
     const int lane = lane_id();
-    const int64_t r = n0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n1) return;
+    const int64_t pos = n0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pos >= n1) return;
+    const int64_t r = ids ? (int64_t)ids[pos] : pos;
     const float* xp = X + (size_t)r * pitch;
     float m = 0.f;
     bool fin = true;
@@ -392,12 +398,25 @@ int launch_h16_rows(const float* X, const float* norms, int64_t n0, int64_t n1, 
     const int64_t rows = n1 - n0;
     if (rows <= 0) return 0;
     hipLaunchKernelGGL(k_h16_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, X, norms, n0, n1, pitch, metric,
-                       H, aux, err);
+                       H, aux, err, (const uint32_t*)nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_h16_rows_ids(const float* X, const float* norms, const uint32_t* ids, int64_t m, int pitch, int metric,
+                        uint16_t* H, float2* aux, float* err, hipStream_t s) {
+    if (m <= 0) return 0;
+    hipLaunchKernelGGL(k_h16_rows, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s, X, norms, (int64_t)0, m, pitch,
+                       metric, H, aux, err, ids);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_norms(const float* X, int64_t n0, int64_t n1, int pitch, int lpr, int vpl, float* out, hipStream_t s) {
     return with_cfg(lpr, vpl, [&](auto c) { return launch_norms_t<Cfg<c.L, c.V>>(X, n0, n1, pitch, out, s); });
+}
+
+int launch_norms_ids(const float* X, const uint32_t* ids, int64_t m, int pitch, int lpr, int vpl, float* out,
+                     hipStream_t s) {
+    return with_cfg(lpr, vpl, [&](auto c) { return launch_norms_t<Cfg<c.L, c.V>>(X, 0, m, pitch, out, s, ids); });
 }
 
 int launch_sweep(const float* q, const float* X, int64_t n, int pitch, int lpr, int vpl, int metric, float* out,

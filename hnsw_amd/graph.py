@@ -487,6 +487,63 @@ class Graph:
                                          vecs.shape[1], _ptr(out, C.c_uint8)))
         return out[: len(keys)].astype(bool)
 
+    # -- update: stored rows re-embedded in place (mhnsw_update) ---------------------
+    def Update(self, nodes: Sequence[Node]) -> List[bool]:
+        """New vectors for present keys, in place: rows keep their ids, levels and filter
+        bits, the graph around them is relinked on the device.  -> which keys were present
+        (an absent or deleted key is not added).  Batch and flat build modes."""
+        if not nodes:
+            return []
+        vecs = [np.asarray(n.Value, dtype=np.float32).ravel() for n in nodes]
+        self._sync()
+        keys = [n.Key for n in nodes]
+        imgs = np.ascontiguousarray(self.encode_keys(keys), np.int64)
+        known = np.ones(len(imgs), bool)
+        if self._kt == "str":
+            # strings the graph never saw have no label (one image for all of them): they are
+            # absent, and the engine's check of repeated keys is made here
+            if len(set(keys)) != len(keys):
+                dup = next(k for i, k in enumerate(keys) if k in keys[:i])
+                raise HnswError(-1, f"duplicate key {dup!r} in update")
+            known = imgs != np.iinfo(np.int64).min
+        out = np.zeros(len(imgs), bool)
+        if known.any():
+            out[known] = self.update_arrays(imgs[known], np.stack(vecs)[known])
+        for n, v, ok in zip(nodes, vecs, out):
+            if ok:
+                self._values[n.Key] = v
+        return [bool(x) for x in out]
+
+    def update_arrays(self, keys, vecs) -> np.ndarray:
+        """Array form of Update: keys int64[n] (engine images), vecs float32[n, dim] (host)."""
+        self._sync()
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        vecs = _f32(vecs).reshape(len(keys), -1)
+        out = np.zeros(max(len(keys), 1), np.uint8)
+        self._check(load().mhnsw_update(self._h, _ptr(keys, C.c_int64), _ptr(vecs, C.c_float), len(keys),
+                                        vecs.shape[1], _ptr(out, C.c_uint8)))
+        return out[: len(keys)].astype(bool)
+
+    def update_device(self, keys, vecs_dev_ptr: int, n: int, dim: int) -> np.ndarray:
+        """update_arrays with the vectors already resident in HBM (device pointer)."""
+        self._sync()
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        out = np.zeros(max(n, 1), np.uint8)
+        self._check(load().mhnsw_update_device(self._h, _ptr(keys, C.c_int64), C.c_void_p(vecs_dev_ptr), n, dim,
+                                               _ptr(out, C.c_uint8)))
+        return out[:n].astype(bool)
+
+    def Upsert(self, nodes: Sequence[Node]) -> List[bool]:
+        """Update the present keys, BatchAdd the absent ones (in their order in `nodes`).
+        -> which keys were present.  A key repeated in the call is the engine's error."""
+        if not nodes:
+            return []
+        found = self.Update(nodes)
+        fresh = [n for n, ok in zip(nodes, found) if not ok]
+        if fresh:
+            self.BatchAdd(fresh)
+        return found
+
     def contains(self, keys) -> np.ndarray:
         """Which keys have a live node (engine key images for a list of Go keys)."""
         imgs = np.ascontiguousarray(self.encode_keys(list(keys)), np.int64)
@@ -862,6 +919,17 @@ class Graph:
         self._check(lib.mhnsw_export(self._h, _ptr(keys, C.c_int64), _ptr(vecs, C.c_float), _ptr(deg, C.c_int32),
                                      _ptr(adj, C.c_int32), cap, _ptr(entry, C.c_int32), _ptr(dead, C.c_uint8)))
         return dict(keys=keys, vecs=vecs, deg=deg, adj=adj, entry=entry[:L], dead=dead[:N])
+
+    def export_edge_dist(self) -> np.ndarray:
+        """The stored edge distances, float32[L, N, cap] in the layout of export()'s adj
+        (0 where adj is -1): what the insert's and the repair's selections rank by."""
+        lib = load()
+        N, dim, L, cap = C.c_int64(), C.c_int(), C.c_int(), C.c_int()
+        self._check(lib.mhnsw_export_sizes(self._h, C.byref(N), C.byref(dim), C.byref(L), C.byref(cap)))
+        adjd = np.zeros((L.value, N.value, cap.value), np.float32)
+        if adjd.size:
+            self._check(lib.mhnsw_export_edge_dist(self._h, _ptr(adjd, C.c_float), cap.value))
+        return adjd
 
     # -- encode.go:128-262 binary format ------------------------------------------
     def _kind(self, key_kind):

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <functional>
 #include <initializer_list>
+#include <limits>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -537,6 +538,69 @@ class Graph {  // graph.go:305-332
         const int rc = mhnsw_compact(h_, &removed);
         if (rc < 0) return {0, make_error(rc, h_)};
         return {removed, {}};
+    }
+
+    // Update (mhnsw.h "Update"): new vectors for present keys, in place -- rows keep their ids,
+    // levels and filter bits, the graph around them is relinked on the device.  first[i]: nodes[i]'s
+    // key was present (an absent or deleted key is not added).  Batch and flat build modes; a key
+    // repeated in the call is MHNSW_EINVAL, and every error leaves the graph as it was.
+    std::pair<std::vector<bool>, Error> Update(const std::vector<Node<K>>& nodes) {
+        std::vector<bool> found(nodes.size(), false);
+        if (nodes.empty()) return {found, {}};
+        sync();
+        const size_t d = nodes[0].Value.size();
+        std::vector<K> ks;
+        for (const auto& n : nodes) ks.push_back(n.Key);
+        const std::vector<int64_t> img = Codec::encode(h_, ks, false);
+        // (string keys: a string the graph never saw has no label -- one image for all of them --
+        // so it is absent, and the engine's check of repeated keys is made here)
+        const bool labels = Codec::kind == MHNSW_KEY_STRING;
+        std::vector<size_t> at;  // positions that go to the engine
+        std::vector<int64_t> keys;
+        std::vector<float> flat;
+        for (size_t i = 0; i < nodes.size(); ++i) {
+            if (nodes[i].Value.size() != d) {
+                Error e;
+                e.code = MHNSW_EDIM;
+                e.msg = "embedding dimension mismatch: " + std::to_string(d) + " != " + std::to_string(nodes[i].Value.size());
+                return {found, e};
+            }
+            if (labels) {
+                for (size_t j = 0; j < i; ++j)
+                    if (nodes[j].Key == nodes[i].Key) {
+                        Error e;
+                        e.code = MHNSW_EINVAL;
+                        e.msg = "duplicate key in update";
+                        return {found, e};
+                    }
+                if (img[i] == std::numeric_limits<int64_t>::min()) continue;
+            }
+            at.push_back(i);
+            keys.push_back(img[i]);
+            flat.insert(flat.end(), nodes[i].Value.begin(), nodes[i].Value.end());
+        }
+        if (at.empty()) return {found, {}};
+        std::vector<uint8_t> out(at.size(), 0);
+        const int rc = mhnsw_update(h_, keys.data(), flat.data(), (int64_t)at.size(), (int)d, out.data());
+        if (rc < 0) return {found, make_error(rc, h_)};
+        for (size_t j = 0; j < at.size(); ++j) {
+            if (!out[j]) continue;
+            found[at[j]] = true;
+            values_[nodes[at[j]].Key] = nodes[at[j]].Value;
+        }
+        return {found, {}};
+    }
+
+    // Upsert: Update of the present keys, then BatchAdd of the absent ones in their order.
+    // first[i]: nodes[i]'s key was present.
+    std::pair<std::vector<bool>, Error> Upsert(const std::vector<Node<K>>& nodes) {
+        auto u = Update(nodes);
+        if (u.second) return u;
+        std::vector<Node<K>> fresh;
+        for (size_t i = 0; i < nodes.size(); ++i)
+            if (!u.first[i]) fresh.push_back(nodes[i]);
+        if (!fresh.empty()) u.second = BatchAdd(fresh);
+        return u;
     }
 
    private:

@@ -410,6 +410,49 @@ int mhnsw_replace(mhnsw_index *h, const int64_t *keys, const float *vecs, int64_
  * "last_compact_scratch_bytes". */
 int mhnsw_compact(mhnsw_index *h, int64_t *out_removed);
 
+/* ---- Update: new vectors for present keys, in place ----
+ * Re-embeds stored rows on the device.  out_found[i] = 1 when keys[i] has a
+ * live layer-0 row, else 0: an absent or deleted key is not added and nothing
+ * is written for it (an update, not an upsert; the hosts build Upsert from
+ * it).  A found row keeps its id, key, level, layer membership and filter
+ * bits; its vector, norm, fp16 screening row and exact-path planes become the
+ * new vector's (by row list: work proportional to the rows updated), and the
+ * graph around it is relinked.  Len, the capacity, the deleted rows, every
+ * layer's entry, every filter and the Rng are unchanged (no level is drawn).
+ * Afterwards every layer holds deg <= cap - 1, no duplicate, no self-loop, no
+ * edge to a deleted, absent or foreign row, and every stored edge distance is
+ * the canonical distance between the current vectors of its two rows.
+ *
+ * A call works in chunks of at most min(batch_max, max(batch_min,
+ * batch_ratio_pct % of the live rows)) rows (and at most half of the live
+ * rows).  Per chunk: detach (the Delete path's repair rebuilds every row that
+ * points into the chunk, the chunk's own rows are emptied), overwrite,
+ * re-insert (the batched insert's descend, search and commit over the chunk's
+ * rows at their ids and levels).  While a chunk is detached its descents start
+ * from a member outside it: in the highest layer that has one, the layer's
+ * entry, else its lowest-id live member; rows of layers whose every member is
+ * in the chunk get no links there.  A chunk's rows do not see each other, as a
+ * batch of Add's do not; the link pass (option "batch_link") is not applied to
+ * update chunks.
+ *
+ * BATCH and FLAT build modes (FLAT: the vector refresh of mhnsw_replace, no
+ * links).  Errors leave the index, its maps and its Rng as they were:
+ * MHNSW_EINVAL (a key repeated within the call, null pointers), MHNSW_EDIM,
+ * MHNSW_EUNSUPPORTED on a COMPAT handle ("update needs a batch or flat
+ * (build_mode 1 or 2) handle": there Add of a present key already replaces it)
+ * and on one with a replaced or re-added key or with rows outside layer 0.
+ * Exclusive like Add and Delete; enqueued searches finish first.
+ * Read-only options, of the last update: "last_update_rows",
+ * "last_update_chunks", "last_update_repaired" ((layer, row) pairs whose
+ * adjacency was rebuilt because it pointed at an updated row) and, with
+ * "time_build" 1 (else 0), "last_update_ns" = "last_update_detach_ns" +
+ * "last_update_overwrite_ns" + "last_update_insert_ns" (device time). */
+int mhnsw_update(mhnsw_index *h, const int64_t *keys, const float *vecs, int64_t n, int dim, uint8_t *out_found);
+int mhnsw_update_device(mhnsw_index *h, const int64_t *keys, const float *d_vecs, int64_t n, int dim,
+                        uint8_t *out_found);
+/* edge distances as stored: layout of mhnsw_export's adj ([L*N*cap]), 0 where adj is -1 */
+int mhnsw_export_edge_dist(mhnsw_index *h, float *adjd, int cap);
+
 /* ---- DistanceFunc (distance.go:12-23): batched sweep of one query over n rows ---- */
 int mhnsw_distance(int metric, const float *q, const float *X, int64_t n, int dim, float *out);
 int mhnsw_distance_device(int metric, const float *d_q, const float *d_X, int64_t n, int dim, float *d_out,
