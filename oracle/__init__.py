@@ -22,6 +22,34 @@ MODE_COMPAT, MODE_BEAM, MODE_EXACT = 0, 1, 2
 _lib = None
 
 
+class BatchCfg(C.Structure):
+    """og_batch_cfg (oracle.h): the engine's build options under its own defaults"""
+    _fields_ = [(f, C.c_int) for f in ("efc", "upper_efc", "heuristic", "keep_pruned", "alpha_pct", "expand",
+                                       "batch_min", "batch_max", "batch_ratio_pct", "batch_link", "batch_link_ef",
+                                       "inc_cap")]
+
+
+# the engine's option names -> og_batch_cfg fields, and the engine's defaults (index.hpp)
+_CFG_NAMES = dict(ef_construction="efc", prune_alpha_pct="alpha_pct", build_expand="expand")
+_CFG_DEFAULTS = dict(efc=0, upper_efc=0, heuristic=1, keep_pruned=0, alpha_pct=100, expand=4, batch_min=1,
+                     batch_max=65536, batch_ratio_pct=5, batch_link=0, batch_link_ef=0, inc_cap=64)
+# og_add_batch / og_update counters (oracle.h OG_C_*)
+COUNTERS = ("batches", "dropped_proposals", "overflow_commits", "rule_drops", "fills", "id_ties", "dead_skipped",
+            "link_rows", "link_edges", "mutual", "update_chunks", "repaired", "truncated_commits", "commit_drops")
+
+
+def batch_cfg(**opts):
+    """BatchCfg from the engine's option names (ef_construction, prune_alpha_pct, build_expand, ...)
+    or the struct's own; what is not named keeps the engine's default."""
+    v = dict(_CFG_DEFAULTS)
+    for k, x in opts.items():
+        k = _CFG_NAMES.get(k, k)
+        if k not in v:
+            raise KeyError(k)
+        v[k] = int(x)
+    return BatchCfg(**v)
+
+
 def build():
     subprocess.check_call(["make", "-s", "-C", _HERE])
 
@@ -36,6 +64,8 @@ def lib():
         f32p, i32p, i64p = P(C.c_float), P(C.c_int32), P(C.c_int64)
         L.og_distance.restype = C.c_float
         L.og_distance.argtypes = [C.c_int, C.c_int, f32p, f32p, C.c_int]
+        L.og_distance_pairs.restype = None
+        L.og_distance_pairs.argtypes = [C.c_int, C.c_int, f32p, C.c_int, i32p, i32p, C.c_int64, f32p]
         L.og_dev_norm.restype = C.c_float
         L.og_dev_norm.argtypes = [f32p, C.c_int]
         L.og_heap_run.restype = C.c_int
@@ -78,6 +108,10 @@ def lib():
                                 i32p, i32p, u8p]
         L.og_search_negatives.argtypes = [C.c_void_p, f32p, C.c_int64, C.c_int, f32p, i32p, C.c_int, C.c_float,
                                           C.c_int, C.c_int, C.c_int, i64p, f32p, i32p]
+        L.og_export_edge_dist.argtypes = [C.c_void_p, f32p, C.c_int]
+        L.og_add_batch.argtypes = [C.c_void_p, i64p, f32p, C.c_int64, C.c_int, i32p, P(BatchCfg), i64p]
+        L.og_update.argtypes = [C.c_void_p, i64p, f32p, C.c_int64, C.c_int, P(BatchCfg), u8p, i64p]
+        L.og_set_batch_descending.argtypes = [C.c_void_p, C.c_int]
         L.og_stats.argtypes = [C.c_void_p, i64p]
         L.og_reset_stats.argtypes = [C.c_void_p]
         _lib = L
@@ -95,6 +129,18 @@ def f32(a):
 def distance(metric, order, a, b):
     a, b = f32(a), f32(b)
     return float(lib().og_distance(metric, order, _p(a, C.c_float), _p(b, C.c_float), a.size))
+
+
+def distance_pairs(metric, order, rows, ia, ib):
+    """float32[len(ia)]: distance(rows[ia[p]], rows[ib[p]])"""
+    rows = f32(rows)
+    ia = np.ascontiguousarray(ia, np.int32)
+    ib = np.ascontiguousarray(ib, np.int32)
+    out = np.zeros(len(ia), np.float32)
+    if len(ia):
+        lib().og_distance_pairs(metric, order, _p(rows, C.c_float), rows.shape[1], _p(ia, C.c_int32),
+                                _p(ib, C.c_int32), len(ia), _p(out, C.c_float))
+    return out
 
 
 def dev_norm(a):
@@ -253,6 +299,45 @@ class Graph:
         self._check(lib().og_export(self._h, _p(keys, C.c_int64), _p(vecs, C.c_float), _p(deg, C.c_int32),
                                     _p(adj, C.c_int32), cap, _p(entry, C.c_int32), _p(dead, C.c_uint8)))
         return dict(keys=keys, vecs=vecs, deg=deg, adj=adj, entry=entry[:L], dead=dead[:N])
+
+    def export_edge_dist(self):
+        """The stored edge distances, float32[L, N, cap] in the layout of export()'s adj (0 past
+        the degree), as hnsw_amd's Graph.export_edge_dist."""
+        N, dim, L, cap = C.c_int64(), C.c_int(), C.c_int(), C.c_int()
+        lib().og_export_sizes(self._h, C.byref(N), C.byref(dim), C.byref(L), C.byref(cap))
+        adjd = np.zeros((L.value, N.value, cap.value), np.float32)
+        if adjd.size:
+            self._check(lib().og_export_edge_dist(self._h, _p(adjd, C.c_float), cap.value))
+        return adjd
+
+    def set_batch_descending(self, on):
+        """Test knob: a batch's rows are taken in descending order (same graph)."""
+        lib().og_set_batch_descending(self._h, int(bool(on)))
+
+    def add_batch(self, keys, vecs, levels, **opts):
+        """The engine's batched insert (run_build_batch), restated; opts: batch_cfg().
+        Returns the call's counters (COUNTERS)."""
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        vecs = f32(vecs).reshape(len(keys), -1)
+        lv = np.ascontiguousarray(levels, dtype=np.int32)
+        assert len(lv) == len(keys)
+        cfg = batch_cfg(**opts)
+        cn = np.zeros(16, np.int64)
+        self._check(lib().og_add_batch(self._h, _p(keys, C.c_int64), _p(vecs, C.c_float), len(keys), vecs.shape[1],
+                                       _p(lv, C.c_int32), C.byref(cfg), _p(cn, C.c_int64)))
+        return dict(zip(COUNTERS, cn.tolist()))
+
+    def update(self, keys, vecs, **opts):
+        """The engine's in-place update (mhnsw_update), restated; opts: batch_cfg().
+        Returns (found bool[n], the call's counters)."""
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        vecs = f32(vecs).reshape(len(keys), -1)
+        cfg = batch_cfg(**opts)
+        cn = np.zeros(16, np.int64)
+        out = np.zeros(max(len(keys), 1), np.uint8)
+        self._check(lib().og_update(self._h, _p(keys, C.c_int64), _p(vecs, C.c_float), len(keys), vecs.shape[1],
+                                    C.byref(cfg), _p(out, C.c_uint8), _p(cn, C.c_int64)))
+        return out[: len(keys)].astype(bool), dict(zip(COUNTERS, cn.tolist()))
 
     def delete(self, keys, mode=0, heuristic=1, keep_pruned=0):
         """Graph.BatchDelete (graph.go:868-895); mode 0 = the reference's

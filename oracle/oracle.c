@@ -106,6 +106,14 @@ float og_distance(int metric, int order, const float *a, const float *b, int dim
     return sqrtf(og_dev_sum(a, b, dim, 1));
 }
 
+/* out[p] = og_distance(rows[ia[p]], rows[ib[p]]): the canonical distance of many
+ * pairs of one row store in one call (the edge-distance checks of tests/) */
+void og_distance_pairs(int metric, int order, const float *rows, int dim, const int32_t *ia, const int32_t *ib,
+                       int64_t npairs, float *out) {
+    for (int64_t p = 0; p < npairs; ++p)
+        out[p] = og_distance(metric, order, rows + (size_t)ia[p] * (size_t)dim, rows + (size_t)ib[p] * (size_t)dim, dim);
+}
+
 /* ------------------------------------------------------------------------ */
 /* Go container/heap restatement (heap/heap.go + container/heap)             */
 /* ------------------------------------------------------------------------ */
@@ -239,6 +247,7 @@ double og_rng_next(uint64_t *state) {
 typedef struct {
     int32_t *deg; /* -2 absent, -1 nil neighbor map, >=0 count */
     int32_t *adj; /* [cap_nodes * acap] */
+    float *adjd;  /* [cap_nodes * acap] stored edge distances (batched insert, repair; 0 elsewhere) */
     int64_t count;
     int32_t entry;
 } og_layer;
@@ -282,6 +291,7 @@ struct og_graph {
     int32_t *kvals;
     int64_t kcap, kn;
     og_scratch scr;
+    int batch_desc; /* test knob: a batch's rows are processed in descending id (og_set_batch_descending) */
     int64_t stats[4];
     char err[256];
 };
@@ -404,6 +414,7 @@ static void free_layers(og_graph *g) {
     for (int i = 0; i < g->nlayers; ++i) {
         free(g->layers[i].deg);
         free(g->layers[i].adj);
+        free(g->layers[i].adjd);
     }
     free(g->layers);
     g->layers = NULL;
@@ -503,10 +514,14 @@ static int ensure_nodes(og_graph *g, int64_t need) {
         og_layer *L = &g->layers[l];
         int32_t *d = (int32_t *)realloc(L->deg, sizeof(int32_t) * (size_t)nc);
         int32_t *a = (int32_t *)realloc(L->adj, sizeof(int32_t) * (size_t)nc * (size_t)g->acap);
-        if (!d || !a) return -1;
+        float *ad = (float *)realloc(L->adjd, sizeof(float) * (size_t)nc * (size_t)g->acap);
+        if (d) L->deg = d;
+        if (a) L->adj = a;
+        if (ad) L->adjd = ad;
+        if (!d || !a || !ad) return -1;
         for (int64_t i = g->cap_nodes; i < nc; ++i) d[i] = -2;
-        L->deg = d;
-        L->adj = a;
+        memset(ad + (size_t)g->cap_nodes * (size_t)g->acap, 0,
+               sizeof(float) * (size_t)(nc - g->cap_nodes) * (size_t)g->acap);
     }
     g->cap_nodes = nc;
     return 0;
@@ -522,9 +537,10 @@ static int add_layer(og_graph *g) {
     int64_t c = g->cap_nodes ? g->cap_nodes : 1;
     L->deg = (int32_t *)malloc(sizeof(int32_t) * (size_t)c);
     L->adj = (int32_t *)malloc(sizeof(int32_t) * (size_t)c * (size_t)g->acap);
-    if (!L->deg || !L->adj) return -1;
+    L->adjd = (float *)calloc((size_t)c * (size_t)g->acap, sizeof(float));
+    g->nlayers++; /* (owned from here on: free_layers releases whatever was allocated) */
+    if (!L->deg || !L->adj || !L->adjd) return -1;
     for (int64_t i = 0; i < c; ++i) L->deg[i] = -2;
-    g->nlayers++;
     return 0;
 }
 
@@ -534,11 +550,21 @@ static int ensure_acap(og_graph *g, int need) {
     for (int l = 0; l < g->nlayers; ++l) {
         og_layer *L = &g->layers[l];
         int32_t *a = (int32_t *)malloc(sizeof(int32_t) * (size_t)(g->cap_nodes ? g->cap_nodes : 1) * (size_t)need);
-        if (!a) return -1;
+        float *ad = (float *)calloc((size_t)(g->cap_nodes ? g->cap_nodes : 1) * (size_t)need, sizeof(float));
+        if (!a || !ad) {
+            free(a);
+            free(ad);
+            return -1;
+        }
         for (int64_t i = 0; i < g->cap_nodes; ++i)
-            for (int j = 0; j < L->deg[i] && L->deg[i] > 0; ++j) a[i * need + j] = L->adj[i * g->acap + j];
+            for (int j = 0; j < L->deg[i] && L->deg[i] > 0; ++j) {
+                a[i * need + j] = L->adj[i * g->acap + j];
+                ad[i * need + j] = L->adjd[i * g->acap + j];
+            }
         free(L->adj);
+        free(L->adjd);
         L->adj = a;
+        L->adjd = ad;
     }
     g->acap = need;
     return 0;
@@ -1048,10 +1074,12 @@ static int rp_cmp(const void *a, const void *b) {
  * batched insert (HNSW diversity heuristic, optional keep-pruned fill).  Rows
  * of deleted nodes are read, never written, so rows are independent. */
 #define OG_REPAIR_POOL 256
-static void repair_layer(og_graph *g, int l, int mcap, int heuristic, int keep_pruned) {
+static int64_t repair_layer(og_graph *g, int l, int mcap, int heuristic, int keep_pruned) {
     og_layer *L = &g->layers[l];
     rp_t *pool = (rp_t *)malloc(sizeof(rp_t) * OG_REPAIR_POOL);
     int32_t *sel = (int32_t *)malloc(sizeof(int32_t) * (size_t)g->acap);
+    float *seld = (float *)malloc(sizeof(float) * (size_t)g->acap);
+    int64_t repaired = 0;
     for (int64_t v = 0; v < g->n; ++v) {
         int d = L->deg[v];
         if (g->dead[v] || d <= 0) continue;
@@ -1084,21 +1112,34 @@ static void repair_layer(og_graph *g, int l, int mcap, int heuristic, int keep_p
                     g->stats[2]++;
                     if (dist_nodes(g, sel[s2], pool[i].id, g->metric) < pool[i].d) good = 0;
                 }
-            if (good) sel[ns++] = pool[i].id;
+            if (good) {
+                seld[ns] = pool[i].d;
+                sel[ns++] = pool[i].id;
+            }
         }
         if (keep_pruned)
             for (int i = 0; i < np && ns < mcap; ++i) {
                 if (i > 0 && pool[i].id == pool[i - 1].id) continue;
                 int have = 0;
                 for (int s2 = 0; s2 < ns; ++s2) have |= sel[s2] == pool[i].id;
-                if (!have) sel[ns++] = pool[i].id;
+                if (!have) {
+                    seld[ns] = pool[i].d;
+                    sel[ns++] = pool[i].id;
+                }
             }
         int32_t *w = L->adj + (size_t)v * g->acap;
-        for (int i = 0; i < ns; ++i) w[i] = sel[i];
+        float *wd = L->adjd + (size_t)v * g->acap; /* the ranking's distances stay with the edges */
+        for (int i = 0; i < ns; ++i) {
+            w[i] = sel[i];
+            wd[i] = seld[i];
+        }
         L->deg[v] = ns;
+        ++repaired;
     }
     free(pool);
     free(sel);
+    free(seld);
+    return repaired;
 }
 
 /* lowest-id live member, the deterministic stand-in for entry() (graph.go:250-258) */
@@ -1518,4 +1559,534 @@ int og_import(og_graph *g, int64_t N, int dim, int L, int cap, const int64_t *ke
     }
     g->layers_exist = L > 0;
     return OG_OK;
+}
+
+int og_export_edge_dist(og_graph *g, float *adjd, int cap) {
+    for (int l = 0; l < g->nlayers; ++l) {
+        og_layer *L = &g->layers[l];
+        for (int64_t i = 0; i < g->n; ++i) {
+            int d = L->deg[i];
+            if (d > cap) return set_err(g, OG_EINVAL, "export cap too small");
+            float *o = adjd + ((size_t)l * g->n + i) * cap;
+            for (int j = 0; j < cap; ++j) o[j] = (j < d) ? L->adjd[(size_t)i * g->acap + j] : 0.f;
+        }
+    }
+    return OG_OK;
+}
+
+/* ------------------------------------------------------------------------ */
+/* batched insert, link pass, update (the engine's own algorithms)           */
+/* ------------------------------------------------------------------------ */
+/* Written from the contract (include/mhnsw.h, DESIGN.md section 6 and the
+ * comments of build_batch.hpp, build_link.hpp, update.hip), sequentially: a
+ * batch's rows all read layer l as it stood before the batch's commit of l, so
+ * the order in which they are taken cannot matter (og_set_batch_descending
+ * checks that), and a commit ranks a row and its proposals by (distance, id)
+ * whatever their arrival order.  The engine drops a proposal when a row
+ * receives more than inc_cap of them in one commit -- which ones depends on
+ * arrival order there -- so the restatement equals the engine only where
+ * counter OG_C_DROPPED stays 0. */
+
+int og_set_batch_descending(og_graph *g, int on) {
+    g->batch_desc = on != 0;
+    return OG_OK;
+}
+
+typedef struct {
+    int32_t tgt, src;
+    float d;
+    int32_t seq;
+} prop_t;
+
+static int prop_cmp(const void *a, const void *b) {
+    const prop_t *x = (const prop_t *)a, *y = (const prop_t *)b;
+    if (x->tgt != y->tgt) return x->tgt < y->tgt ? -1 : 1;
+    return x->seq < y->seq ? -1 : (x->seq > y->seq);
+}
+
+static int i64_cmp(const void *a, const void *b) {
+    const int64_t x = *(const int64_t *)a, y = *(const int64_t *)b;
+    return x < y ? -1 : (x > y);
+}
+
+/* 1 and *key when a key occurs twice in keys[0, n), 0 when none does, -1 out of memory */
+static int repeated_key(const int64_t *keys, int64_t n, int64_t *key) {
+    int64_t *sk = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n > 0 ? n : 1));
+    if (!sk) return -1;
+    memcpy(sk, keys, sizeof(int64_t) * (size_t)n);
+    qsort(sk, (size_t)n, sizeof(int64_t), i64_cmp);
+    int found = 0;
+    for (int64_t i = 1; i < n && !found; ++i)
+        if (sk[i] == sk[i - 1]) {
+            *key = sk[i];
+            found = 1;
+        }
+    free(sk);
+    return found;
+}
+
+static int level_of(const og_graph *g, int32_t u) {
+    int lv = -1;
+    for (int l = 0; l < g->nlayers; ++l)
+        if (g->layers[l].deg[u] != -2) lv = l;
+    return lv;
+}
+
+/* The neighbour selection of one row from its candidates (ranked by (distance,
+ * id), distances to the row): live candidates in rank order, at most mcap; with
+ * `heuristic` a candidate c is dropped when alpha * d(c, r) < d(u, c) for a
+ * neighbour r kept before it; keep_pruned then fills the row with the dropped
+ * ones, again in rank order. */
+static int select_row(og_graph *g, const og_batch_cfg *c, const bentry *lst, int nl, int mcap, int32_t *sel,
+                      float *seld, int64_t *cn) {
+    const float alpha = (float)c->alpha_pct / 100.0f;
+    int ns = 0;
+    for (int i = 0; i < nl && ns < mcap; ++i) {
+        const int32_t id = lst[i].id;
+        if (g->dead[id]) {
+            cn[OG_C_DEAD_SKIPPED]++;
+            continue;
+        }
+        if (i > 0 && lst[i].d == lst[i - 1].d) cn[OG_C_ID_TIES]++;
+        int good = 1;
+        for (int s = 0; c->heuristic && s < ns && good; ++s) {
+            g->stats[2]++;
+            if (alpha * dist_nodes(g, id, sel[s], g->metric) < lst[i].d) good = 0;
+        }
+        if (!good) {
+            cn[OG_C_RULE_DROPS]++;
+            continue;
+        }
+        sel[ns] = id;
+        seld[ns++] = lst[i].d;
+    }
+    if (c->keep_pruned)
+        for (int i = 0; i < nl && ns < mcap; ++i) {
+            const int32_t id = lst[i].id;
+            if (g->dead[id]) continue;
+            int have = 0;
+            for (int s = 0; s < ns; ++s) have |= sel[s] == id;
+            if (have) continue;
+            sel[ns] = id;
+            seld[ns++] = lst[i].d;
+            cn[OG_C_FILLS]++;
+        }
+    return ns;
+}
+
+/* One touched row v of layer l: the row and the proposals it received, ranked
+ * by (distance to v, id), written in rank order when they fit the row or when
+ * heuristic < 2 (then the best mcap); else the diversity rule with alpha, and
+ * no fill. */
+static void commit_row(og_graph *g, const og_batch_cfg *c, int l, int32_t v, const prop_t *pr, int np, int mcap,
+                       rp_t *e, int64_t *cn) {
+    og_layer *L = &g->layers[l];
+    const float alpha = (float)c->alpha_pct / 100.0f;
+    int32_t *row = L->adj + (size_t)v * g->acap;
+    float *rowd = L->adjd + (size_t)v * g->acap;
+    int d = L->deg[v] < 0 ? 0 : L->deg[v];
+    if (np > c->inc_cap) { /* the engine would drop these (which ones: arrival order) */
+        cn[OG_C_DROPPED] += np - c->inc_cap;
+        np = c->inc_cap;
+    }
+    int tot = 0;
+    for (int j = 0; j < d; ++j) {
+        e[tot].id = row[j];
+        e[tot++].d = rowd[j];
+    }
+    for (int j = 0; j < np; ++j) {
+        e[tot].id = pr[j].src;
+        e[tot++].d = pr[j].d;
+    }
+    qsort(e, (size_t)tot, sizeof(rp_t), rp_cmp);
+    for (int i = 1; i < tot; ++i)
+        if (e[i].d == e[i - 1].d) cn[OG_C_ID_TIES]++;
+    int nk = 0;
+    if (tot <= mcap || c->heuristic < 2) {
+        nk = tot < mcap ? tot : mcap;
+        if (tot > mcap) cn[OG_C_TRUNCATED]++;
+        for (int i = 0; i < nk; ++i) {
+            row[i] = e[i].id;
+            rowd[i] = e[i].d;
+        }
+    } else {
+        cn[OG_C_OVERFLOW]++;
+        for (int i = 0; i < tot && nk < mcap; ++i) {
+            int good = 1;
+            /* (the kept entries sit in e[0, nk): nk <= i, so writing them there loses nothing) */
+            for (int s = 0; s < nk && good; ++s) {
+                g->stats[2]++;
+                if (alpha * dist_nodes(g, e[i].id, e[s].id, g->metric) < e[i].d) good = 0;
+            }
+            if (!good) {
+                cn[OG_C_COMMIT_DROPS]++;
+                continue;
+            }
+            e[nk++] = e[i];
+        }
+        for (int i = 0; i < nk; ++i) {
+            row[i] = e[i].id;
+            rowd[i] = e[i].d;
+        }
+    }
+    L->deg[v] = nk;
+}
+
+static void commit_all(og_graph *g, const og_batch_cfg *c, int l, prop_t *pr, int np, int mcap, rp_t *e,
+                       int64_t *cn) {
+    qsort(pr, (size_t)np, sizeof(prop_t), prop_cmp);
+    for (int a = 0; a < np;) {
+        int b = a;
+        while (b < np && pr[b].tgt == pr[a].tgt) ++b;
+        commit_row(g, c, l, pr[a].tgt, pr + a, b - a, mcap, e, cn);
+        a = b;
+    }
+}
+
+/* One batch: rows[0, nb) (members of their layers already, their own rows
+ * empty), inserted into the layers top..0 from `entry`.  link: the rows are the
+ * ids [n0, n1) and the link pass runs where two or more of them hold the layer. */
+static int batch_layers(og_graph *g, const og_batch_cfg *c, const int32_t *rows, int nb, int top, int32_t entry,
+                        int link, int32_t n0, int32_t n1, int64_t *cn) {
+    const int efc = c->efc > 0 ? c->efc : g->ef;
+    const int mc = g->M0 > g->M ? g->M0 : g->M;
+    if (mc + c->inc_cap > 4096 || c->inc_cap < 1) return set_err(g, OG_EINVAL, "inc_cap out of range");
+    int rc = OG_OK;
+    int32_t *cur = (int32_t *)malloc(sizeof(int32_t) * (size_t)nb);
+    int *lvl = (int *)malloc(sizeof(int) * (size_t)nb);
+    int *st_n = (int *)malloc(sizeof(int) * (size_t)nb);
+    int32_t *st_id = (int32_t *)malloc(sizeof(int32_t) * (size_t)nb * (size_t)mc);
+    float *st_d = (float *)malloc(sizeof(float) * (size_t)nb * (size_t)mc);
+    prop_t *pr = (prop_t *)malloc(sizeof(prop_t) * (size_t)nb * (size_t)mc);
+    bentry *lst = (bentry *)malloc(sizeof(bentry) * (512 + 2));
+    bentry *cu = (bentry *)malloc(sizeof(bentry) * (512 + 2));
+    rp_t *e = (rp_t *)malloc(sizeof(rp_t) * (size_t)(mc + 1 + c->inc_cap));
+    if (!cur || !lvl || !st_n || !st_id || !st_d || !pr || !lst || !cu || !e) {
+        rc = set_err(g, OG_ENOMEM, "out of memory");
+        goto done;
+    }
+    for (int i = 0; i < nb; ++i) {
+        cur[i] = entry;
+        lvl[i] = level_of(g, rows[i]);
+    }
+    cn[OG_C_BATCHES]++;
+    for (int l = top; l >= 0; --l) {
+        og_layer *L = &g->layers[l];
+        const int mcap = l == 0 ? g->M0 : g->M;
+        int ef = l > 0 && c->upper_efc > 0 ? (efc < c->upper_efc ? efc : c->upper_efc) : efc;
+        if (ef < mcap) ef = mcap;
+        if (ef > 512) {
+            rc = set_err(g, OG_EUNSUPPORTED, "candidate list wider than 512 (ef=%d)", ef);
+            goto done;
+        }
+        int np = 0, at_layer = 0;
+        for (int k = 0; k < nb; ++k) {
+            const int i = g->batch_desc ? nb - 1 - k : k;
+            const int32_t u = rows[i];
+            st_n[i] = -1;
+            if (lvl[i] < l) { /* above the row's level: a greedy step */
+                int n = beam_layer_search(g, &g->scr, l, cur[i], 1, vec_of(g, u), g->norms[u], lst, &g->stats[2],
+                                          &g->stats[3], 1);
+                if (n > 0) cur[i] = lst[0].id;
+                continue;
+            }
+            ++at_layer;
+            int n = beam_layer_search(g, &g->scr, l, cur[i], ef, vec_of(g, u), g->norms[u], lst, &g->stats[2],
+                                      &g->stats[3], c->expand);
+            if (n > 0) cur[i] = lst[0].id;
+            st_n[i] = select_row(g, c, lst, n, mcap, st_id + (size_t)i * mc, st_d + (size_t)i * mc, cn);
+            for (int j = 0; j < st_n[i]; ++j) {
+                pr[np].tgt = st_id[(size_t)i * mc + j];
+                pr[np].src = u;
+                pr[np].d = st_d[(size_t)i * mc + j];
+                pr[np].seq = np;
+                ++np;
+            }
+        }
+        for (int i = 0; i < nb; ++i) { /* the rows' own rows: selection order, the list's distances */
+            if (st_n[i] < 0) continue;
+            const int32_t u = rows[i];
+            for (int j = 0; j < st_n[i]; ++j) {
+                L->adj[(size_t)u * g->acap + j] = st_id[(size_t)i * mc + j];
+                L->adjd[(size_t)u * g->acap + j] = st_d[(size_t)i * mc + j];
+            }
+            L->deg[u] = st_n[i];
+        }
+        commit_all(g, c, l, pr, np, mcap, e, cn);
+        if (!link || at_layer < 2) continue;
+        /* The link pass: layer l now holds the batch.  Each of its rows searches the layer
+         * again from its running entry (read, not written) at the link width; its candidates
+         * are its row, then the batch-mates the list holds, in a list of the width's tier. */
+        int lef = ef;
+        if (c->batch_link_ef > 0) {
+            lef = c->batch_link_ef > mcap ? c->batch_link_ef : mcap;
+            if (lef > 512) lef = 512;
+        }
+        const int nc = lef <= 64 ? 64 : lef <= 128 ? 128 : lef <= 256 ? 256 : 512;
+        np = 0;
+        for (int k = 0; k < nb; ++k) {
+            const int i = g->batch_desc ? nb - 1 - k : k;
+            const int32_t u = rows[i];
+            st_n[i] = -1;
+            if (lvl[i] < l) continue;
+            int n = beam_layer_search(g, &g->scr, l, cur[i], lef, vec_of(g, u), g->norms[u], lst, &g->stats[2],
+                                      &g->stats[3], c->expand);
+            const int d0 = L->deg[u] < 0 ? 0 : L->deg[u];
+            const int32_t *row = L->adj + (size_t)u * g->acap;
+            const float *rowd = L->adjd + (size_t)u * g->acap;
+            int ncu = 0;
+            for (int j = 0; j < d0; ++j)
+                if (row[j] != u) beam_insert(cu, &ncu, nc, rowd[j], row[j]);
+            for (int j = 0; j < n; ++j) {
+                const int32_t m = lst[j].id;
+                if (m >= n0 && m < n1 && m != u && !g->dead[m]) beam_insert(cu, &ncu, nc, lst[j].d, m);
+            }
+            int32_t *sel = st_id + (size_t)i * mc;
+            float *seld = st_d + (size_t)i * mc;
+            const int ns = select_row(g, c, cu, ncu, mcap, sel, seld, cn);
+            int nfresh = 0;
+            for (int j = 0; j < ns; ++j) {
+                int inold = 0;
+                for (int t = 0; t < d0; ++t) inold |= row[t] == sel[j];
+                if (inold) continue;
+                ++nfresh;
+                pr[np].tgt = sel[j];
+                pr[np].src = u;
+                pr[np].d = seld[j];
+                pr[np].seq = np;
+                ++np;
+            }
+            if (ns == d0 && !nfresh) continue; /* the same row: nothing staged */
+            st_n[i] = ns;
+            cn[OG_C_LINK_ROWS]++;
+            cn[OG_C_LINK_EDGES] += nfresh;
+        }
+        qsort(pr, (size_t)np, sizeof(prop_t), prop_cmp);
+        for (int i = 0; i < nb; ++i) { /* staged rows replace the rows, less what a waiting proposal repeats */
+            if (st_n[i] < 0) continue;
+            const int32_t u = rows[i];
+            int a = 0, w = 0;
+            while (a < np && pr[a].tgt < u) ++a;
+            for (int j = 0; j < st_n[i]; ++j) {
+                int waiting = 0;
+                for (int b = a, cnt = 0; b < np && pr[b].tgt == u && cnt < c->inc_cap; ++b, ++cnt)
+                    waiting |= pr[b].src == st_id[(size_t)i * mc + j];
+                if (waiting) {
+                    cn[OG_C_MUTUAL]++;
+                    continue;
+                }
+                L->adj[(size_t)u * g->acap + w] = st_id[(size_t)i * mc + j];
+                L->adjd[(size_t)u * g->acap + w] = st_d[(size_t)i * mc + j];
+                ++w;
+            }
+            L->deg[u] = w;
+        }
+        commit_all(g, c, l, pr, np, mcap, e, cn);
+    }
+done:
+    free(cur);
+    free(lvl);
+    free(st_n);
+    free(st_id);
+    free(st_d);
+    free(pr);
+    free(lst);
+    free(cu);
+    free(e);
+    return rc;
+}
+
+static int batch_cfg_check(og_graph *g, const og_batch_cfg *c) {
+    if (c->heuristic < 0 || c->heuristic > 2) return set_err(g, OG_EINVAL, "heuristic must be 0, 1 or 2");
+    if (c->expand < 1 || c->expand > 4) return set_err(g, OG_EINVAL, "expand must be in [1, 4]");
+    if (c->batch_min < 1 || c->batch_max < 1 || c->batch_ratio_pct < 0)
+        return set_err(g, OG_EINVAL, "batch_min and batch_max must be >= 1, batch_ratio_pct >= 0");
+    if (c->alpha_pct < 50 || c->alpha_pct > 400) return set_err(g, OG_EINVAL, "alpha_pct must be in [50, 400]");
+    if (g->M > 63 || g->M0 > 63) return set_err(g, OG_EUNSUPPORTED, "degree caps above 63 unsupported");
+    return OG_OK;
+}
+
+static int64_t batch_size_at(const og_batch_cfg *c, int64_t i) {
+    int64_t b = (int64_t)((double)i * c->batch_ratio_pct / 100.0);
+    if (b < c->batch_min) b = c->batch_min;
+    if (b > c->batch_max) b = c->batch_max;
+    return b;
+}
+
+int og_add_batch(og_graph *g, const int64_t *keys, const float *vecs, int64_t n, int dim, const int32_t *levels,
+                 const og_batch_cfg *c, int64_t *out_counters) {
+    int64_t cn[OG_NCOUNTERS] = {0};
+    int rc = og_validate(g);
+    if (rc) return rc;
+    if ((rc = batch_cfg_check(g, c))) return rc;
+    if (!levels) return set_err(g, OG_EINVAL, "og_add_batch needs the levels");
+    if (n <= 0) return OG_OK;
+    if (g->layers_exist && g->dim != dim)
+        return set_err(g, OG_EDIM, "embedding dimension mismatch: %d != %d", g->dim, dim);
+    for (int64_t i = 0; i < n; ++i) {
+        if (levels[i] < 0) return set_err(g, OG_EINVAL, "invalid level: %d", levels[i]);
+        if (hget(g, keys[i]) >= 0)
+            return set_err(g, OG_EUNSUPPORTED, "duplicate key %lld: replacement needs the compat build mode",
+                           (long long)keys[i]);
+    }
+    int64_t dk = 0;
+    if ((rc = repeated_key(keys, n, &dk)) < 0) return set_err(g, OG_ENOMEM, "out of memory");
+    if (rc) return set_err(g, OG_EUNSUPPORTED, "duplicate key %lld: replacement needs the compat build mode", (long long)dk);
+    if (ensure_acap(g, (g->M > g->M0 ? g->M : g->M0) + 1)) return set_err(g, OG_ENOMEM, "out of memory");
+    if (!g->layers_exist) g->dim = dim;
+    /* the live top layer and its entry before this call (-1: an empty graph) */
+    int top = -1;
+    int32_t entry = -1;
+    if (g->layers_exist && og_len(g) > 0) {
+        top = top_live_layer(g);
+        entry = g->layers[top].entry;
+    }
+    const int64_t n0 = g->n;
+    if (ensure_nodes(g, n0 + n + 1)) return set_err(g, OG_ENOMEM, "out of memory");
+    /* the rows and their layer membership, in call order */
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t id = (int32_t)(n0 + i);
+        while (levels[i] >= g->nlayers)
+            if (add_layer(g)) return set_err(g, OG_ENOMEM, "out of memory");
+        g->n = id + 1;
+        g->keys[id] = keys[i];
+        g->kid[id] = kid_get(g, keys[i], id);
+        g->prev_live[id] = -1;
+        g->dead[id] = 0;
+        memcpy(g->vecs + (size_t)id * dim, vecs + (size_t)i * dim, sizeof(float) * (size_t)dim);
+        g->norms[id] = og_dev_norm(vecs + (size_t)i * dim, dim);
+        if (hput(g, keys[i], id)) return set_err(g, OG_ENOMEM, "out of memory");
+        for (int l = 0; l <= levels[i]; ++l) {
+            og_layer *L = &g->layers[l];
+            if (L->count == 0) L->entry = id;
+            L->count++;
+            L->deg[id] = 0;
+        }
+    }
+    g->layers_exist = 1;
+    int32_t *rows = (int32_t *)malloc(sizeof(int32_t) * (size_t)n);
+    if (!rows) return set_err(g, OG_ENOMEM, "out of memory");
+    int64_t i = 0;
+    while (i < n && rc == OG_OK) {
+        const int lv = levels[i];
+        const int32_t id = (int32_t)(n0 + i);
+        if (top < 0) { /* the first row of the graph: alone in all its layers */
+            top = lv;
+            entry = id;
+            ++i;
+            continue;
+        }
+        if (lv > top) { /* new top layers: a batch of one, then it is the entry */
+            rows[0] = id;
+            rc = batch_layers(g, c, rows, 1, top, entry, 0, id, id + 1, cn);
+            top = lv;
+            entry = id;
+            ++i;
+            continue;
+        }
+        const int64_t bsz = batch_size_at(c, id);
+        int64_t j = i;
+        while (j < n && j - i < bsz && levels[j] <= top) ++j; /* cut short before a row above the top */
+        for (int64_t t = i; t < j; ++t) rows[t - i] = (int32_t)(n0 + t);
+        rc = batch_layers(g, c, rows, (int)(j - i), top, entry, c->batch_link != 0 && j - i >= 2, (int32_t)(n0 + i),
+                          (int32_t)(n0 + j), cn);
+        i = j;
+    }
+    free(rows);
+    if (out_counters)
+        for (int k = 0; k < OG_NCOUNTERS; ++k) out_counters[k] += cn[k];
+    return rc;
+}
+
+#define OG_UPDATE_MARK 2
+
+int og_update(og_graph *g, const int64_t *keys, const float *vecs, int64_t n, int dim, const og_batch_cfg *c,
+              uint8_t *out_found, int64_t *out_counters) {
+    int64_t cn[OG_NCOUNTERS] = {0};
+    int rc = og_validate(g);
+    if (rc) return rc;
+    if ((rc = batch_cfg_check(g, c))) return rc;
+    if (n <= 0) return OG_OK;
+    if (g->layers_exist && g->dim != dim)
+        return set_err(g, OG_EDIM, "embedding dimension mismatch: %d != %d", g->dim, dim);
+    int64_t dk = 0;
+    if ((rc = repeated_key(keys, n, &dk)) < 0) return set_err(g, OG_ENOMEM, "out of memory");
+    if (rc) return set_err(g, OG_EINVAL, "duplicate key %lld in update", (long long)dk);
+    int32_t *ids = (int32_t *)malloc(sizeof(int32_t) * (size_t)n);
+    int64_t *from = (int64_t *)malloc(sizeof(int64_t) * (size_t)n);
+    uint8_t *in_u = (uint8_t *)calloc((size_t)(g->n > 0 ? g->n : 1), 1);
+    if (!ids || !from || !in_u) {
+        rc = set_err(g, OG_ENOMEM, "out of memory");
+        goto done;
+    }
+    int64_t m = 0;
+    for (int64_t i = 0; i < n; ++i) { /* the found keys' rows, in call order */
+        out_found[i] = 0;
+        const int32_t r = hget(g, keys[i]);
+        if (r < 0 || g->dead[r] || !member(g, 0, r)) continue;
+        out_found[i] = 1;
+        ids[m] = r;
+        from[m++] = i;
+    }
+    if (m == 0) goto done;
+    const int64_t live = og_len(g);
+    int64_t bsz = batch_size_at(c, live);
+    if (bsz > live / 2) bsz = live / 2;
+    if (bsz < 1) bsz = 1;
+    for (int64_t c0 = 0; c0 < m && rc == OG_OK; c0 += bsz) {
+        const int64_t cnt = bsz < m - c0 ? bsz : m - c0;
+        cn[OG_C_UPD_CHUNKS]++;
+        /* detach: the chunk's rows marked, every live row that points at one rebuilt over the
+         * old vectors (Delete's repair: the rule without alpha), their own rows emptied, the
+         * edges that deleted rows held into the chunk dropped, the marks cleared */
+        for (int64_t j = c0; j < c0 + cnt; ++j) g->dead[ids[j]] = OG_UPDATE_MARK;
+        for (int l = 0; l < g->nlayers; ++l)
+            cn[OG_C_REPAIRED] += repair_layer(g, l, l == 0 ? g->M0 : g->M, c->heuristic, c->keep_pruned);
+        for (int l = 0; l < g->nlayers; ++l) {
+            og_layer *L = &g->layers[l];
+            for (int64_t r = 0; r < g->n; ++r) {
+                const int d = L->deg[r];
+                if (!g->dead[r] || d <= 0) continue;
+                int32_t *a = L->adj + (size_t)r * g->acap;
+                float *ad = L->adjd + (size_t)r * g->acap;
+                int w = 0;
+                if (g->dead[r] != OG_UPDATE_MARK)
+                    for (int j = 0; j < d; ++j) {
+                        if (g->dead[a[j]] == OG_UPDATE_MARK) continue;
+                        a[w] = a[j];
+                        ad[w] = ad[j];
+                        ++w;
+                    }
+                L->deg[r] = w;
+            }
+        }
+        for (int64_t j = c0; j < c0 + cnt; ++j) g->dead[ids[j]] = 0;
+        /* overwrite: the vectors and their norms */
+        for (int64_t j = c0; j < c0 + cnt; ++j) {
+            const float *v = vecs + (size_t)from[j] * dim;
+            memcpy(g->vecs + (size_t)ids[j] * dim, v, sizeof(float) * (size_t)dim);
+            g->norms[ids[j]] = og_dev_norm(v, dim);
+        }
+        /* re-insert from an entry outside the chunk: the highest layer with a live member
+         * outside it; there the layer's entry, else its lowest-id live member outside it */
+        for (int64_t j = c0; j < c0 + cnt; ++j) in_u[ids[j]] = 1;
+        int top = top_live_layer(g);
+        int32_t entry = -1;
+        for (; top >= 0 && entry < 0; --top) {
+            const og_layer *L = &g->layers[top];
+            if (member(g, top, L->entry) && !in_u[L->entry]) entry = L->entry;
+            for (int64_t r = 0; r < g->n && entry < 0; ++r)
+                if (member(g, top, (int32_t)r) && !in_u[r]) entry = (int32_t)r;
+            if (entry >= 0) break;
+        }
+        for (int64_t j = c0; j < c0 + cnt; ++j) in_u[ids[j]] = 0;
+        if (entry >= 0) rc = batch_layers(g, c, ids + c0, (int)cnt, top, entry, 0, 0, 0, cn);
+    }
+done:
+    free(ids);
+    free(from);
+    free(in_u);
+    if (out_counters)
+        for (int k = 0; k < OG_NCOUNTERS; ++k) out_counters[k] += cn[k];
+    return rc;
 }

@@ -23,6 +23,16 @@
  *   parquet/graph.go:924-1076, arrow/graph.go:576-659   beam-search precedent
  *
  * Parity pinning: see oracle.c header and tests/test_oracle_golden.py.
+ *
+ * The engine's own algorithms (no counterpart in the reference) are restated
+ * here as well, from their contract (include/mhnsw.h):
+ *   beam search (og_search MODE_BEAM, og_set_search_expand), the repair delete
+ *   (og_delete mode 1), and the batched insert, its link pass and the in-place
+ *   update (og_add_batch, og_update, og_export_edge_dist).  The last three are
+ *   sequential where the engine is parallel; they equal the engine's export and
+ *   stored edge distances bit for bit wherever no reverse proposal is dropped
+ *   (counter OG_C_DROPPED; tests/test_batch_oracle.py on the CPU against numpy
+ *   and an engine-built fixture, tests/test_gpu_batch_oracle.py on the device).
  */
 #ifndef MHNSW_ORACLE_H
 #define MHNSW_ORACLE_H
@@ -58,6 +68,9 @@ typedef struct og_graph og_graph;
 float og_distance(int metric, int order, const float *a, const float *b, int dim);
 float og_dev_sum(const float *a, const float *b, int dim, int square_diff);
 float og_dev_norm(const float *a, int dim);
+/* out[p] = og_distance(rows[ia[p]], rows[ib[p]]) for rows[*][dim] */
+void og_distance_pairs(int metric, int order, const float *rows, int dim, const int32_t *ia, const int32_t *ib,
+                       int64_t npairs, float *out);
 
 /* ---- Go container/heap restatement (heap/heap.go) on (dist,id) pairs ----
  * ops: 0=push(d,id) 1=pop 2=poplast.  Applies a sequence of ops to an
@@ -134,6 +147,70 @@ int og_export(og_graph *g, int64_t *keys, float *vecs, int32_t *deg, int32_t *ad
 int og_import(og_graph *g, int64_t N, int dim, int L, int cap, const int64_t *keys,
               const float *vecs, const int32_t *deg, const int32_t *adj, const int32_t *entry,
               const uint8_t *dead);
+
+/* The stored edge distances, [L][N][cap] in the layout of og_export's adj and of
+ * mhnsw_export_edge_dist (0 past the degree): what the batched insert, the link
+ * pass and the repair ranked by -- the search list's distance of the edge,
+ * carried to the other end by the proposal.  Rows written by the compat insert
+ * (og_add) carry none. */
+int og_export_edge_dist(og_graph *g, float *adjd, int cap);
+
+/* ---- the engine's batched insert, link pass and update, restated ----------
+ * Options as the engine's (include/mhnsw.h): efc = ef_construction (0: EfSearch),
+ * upper_efc, heuristic (0 closest, 1 diversity rule on the new row, 2 also on
+ * overflowing rows), keep_pruned, alpha_pct = prune_alpha_pct, expand =
+ * build_expand, the batch schedule, batch_link / batch_link_ef, and inc_cap, the
+ * proposals a row can receive in one commit (the engine's 64). */
+typedef struct {
+    int efc, upper_efc, heuristic, keep_pruned, alpha_pct, expand;
+    int batch_min, batch_max, batch_ratio_pct;
+    int batch_link, batch_link_ef;
+    int inc_cap;
+} og_batch_cfg;
+
+/* out_counters[OG_NCOUNTERS], added to (nullable) */
+enum {
+    OG_C_BATCHES = 0,   /* batches run (a row inserted alone above the top is one) */
+    OG_C_DROPPED,       /* proposals past inc_cap in one commit: the engine drops these by arrival
+                           order, so engine and restatement agree only where this stays 0 */
+    OG_C_OVERFLOW,      /* commits that overflowed into the diversity rule (heuristic 2) */
+    OG_C_RULE_DROPS,    /* candidates the rule dropped in a row's own selection */
+    OG_C_FILLS,         /* keep_pruned fills */
+    OG_C_ID_TIES,       /* neighbours in a selection's list or a commit's rank at equal distance: order by id */
+    OG_C_DEAD_SKIPPED,  /* deleted candidates skipped by a selection */
+    OG_C_LINK_ROWS,     /* link pass: rows whose selection changed (one per layer) */
+    OG_C_LINK_EDGES,    /* link pass: batch-mates those selections added */
+    OG_C_MUTUAL,        /* link pass: staged entries left to a waiting proposal (mutual selection) */
+    OG_C_UPD_CHUNKS,    /* update: chunks */
+    OG_C_REPAIRED,      /* update: rows the detach's repair rebuilt */
+    OG_C_TRUNCATED,     /* commits that overflowed and kept the best cap (heuristic < 2) */
+    OG_C_COMMIT_DROPS,  /* candidates the rule dropped in an overflowing commit */
+    OG_NCOUNTERS = 16
+};
+
+/* run_build_batch / run_batch_layers: fresh keys only, levels required.  The
+ * first row of a graph is alone in its layers; a row above the top layer is a
+ * batch of one and then the entry; else a batch holds min(batch_max,
+ * max(batch_min, floor(id * batch_ratio_pct / 100))) rows, cut short before a
+ * row above the top.  Per batch and layer (top to 0) every row reads the layer
+ * as it stood before the batch: greedy step above its level, else the layer
+ * search (width max(efc or upper_efc, row cap), build_expand), the neighbour
+ * selection, its own row and one proposal per neighbour; then the commit, and
+ * with batch_link the link pass and its commit. */
+int og_add_batch(og_graph *g, const int64_t *keys, const float *vecs, int64_t n, int dim, const int32_t *levels,
+                 const og_batch_cfg *cfg, int64_t *out_counters);
+
+/* mhnsw_update: present keys take new vectors in place, in chunks of
+ * max(1, min(batch size at the live count, batch_max, live / 2)) found rows in
+ * call order: detach (Delete's repair over the old vectors, the chunk's rows
+ * emptied, deleted rows' edges into the chunk dropped), overwrite, re-insert as
+ * one batch without link pass from an entry outside the chunk. */
+int og_update(og_graph *g, const int64_t *keys, const float *vecs, int64_t n, int dim, const og_batch_cfg *cfg,
+              uint8_t *out_found, int64_t *out_counters);
+
+/* test knob: a batch's rows are taken in descending instead of ascending order
+ * (the result must not depend on it) */
+int og_set_batch_descending(og_graph *g, int on);
 
 /* counters: [0]=distance evals (search), [1]=expansions (search),
  * [2]=distance evals (build), [3]=expansions (build) */

@@ -1,11 +1,13 @@
 """The batched insert's link pass (option batch_link): after a layer's commit
 every row of the batch searches the layer again and takes the batch-mates it
-finds into its neighbour selection.  The oracle does not restate the batched
-build, so these are properties of the exported graph, oracle replay of the
-searches on it, and comparisons with the unlinked build of the same rows."""
+finds into its neighbour selection.  These are properties of the exported
+graph, oracle replay of the searches on it, comparisons with the unlinked build
+of the same rows, and (test_link_structure_and_replay) the whole export against
+the oracle's restatement of the batched build and the link pass, bit for bit."""
 import numpy as np
 import pytest
 
+from tests import batch_ref as BR
 from tests.test_gpu_parity import _metric_fn, _same_results
 
 pytestmark = pytest.mark.gpu
@@ -122,6 +124,20 @@ def test_link_structure_and_replay(H, O, metric):
     _check_linked(gb, exa, exb, SHAPE["n0"], [SHAPE["m0"]] + [SHAPE["M"]] * 31)
     _check_replay(H, O, gb, exb, Q, metric, SHAPE["M"], SHAPE["m0"])
     assert gb.get_option("last_link_ns") == 0  # (time_build is off)
+    # the restatement (og_add_batch) given the same rows, levels and options builds both graphs:
+    # every field, adj in stored order, and the bits of every stored edge distance
+    n0, nb = SHAPE["n0"], SHAPE["nb"]
+    opts = dict(ef_construction=SHAPE["efc"], heuristic=2, keep_pruned=1)
+    for g, ex, link in ((ga, exa, 0), (gb, exb, 1)):
+        assert g.stats()["dropped_proposals"] == 0
+        lv = BR.levels_of(ex)
+        o = O.Graph(metric=metric, order=O.ORDER_DEV, M=SHAPE["M"], M0=SHAPE["m0"], Ml=0.25, EfSearch=64)
+        cn = o.add_batch(np.arange(n0), X[:n0], lv[:n0], **opts)
+        cl = o.add_batch(np.arange(n0, n0 + nb), X[n0:n0 + nb], lv[n0:], batch_link=link, batch_ratio_pct=0,
+                         batch_max=nb, batch_min=nb, **opts)
+        assert cn["dropped_proposals"] == 0 and cl["dropped_proposals"] == 0
+        assert cl["link_rows"] == g.get_option("last_link_rows") and cl["link_edges"] == g.get_option("last_link_edges")
+        BR.same_export(ex, o.export(), g.export_edge_dist(), o.export_edge_dist(), what=("link", link))
     ga.close()
     gb.close()
 

@@ -1,11 +1,12 @@
 """GPU: the in-place update (mhnsw_update / Graph.update_arrays / Graph.Update): stored rows
 take new vectors, keep their ids, levels, layer membership and filter bits, and the graph
-around them is relinked on the device.  The oracle does not restate the batched build, so
-these are properties of the export, oracle replay of the searches on it, and comparisons with
-the route the call replaces (Delete + Add)."""
+around them is relinked on the device.  These are properties of the export, oracle replay of the searches on
+it, comparisons with the route the call replaces (Delete + Add), and (_check_update) the whole
+export against the oracle's restatement of the build and the update, bit for bit."""
 import numpy as np
 import pytest
 
+from tests import batch_ref as BR
 from tests import compact_ref as CR
 from tests.test_gpu_parity import _metric_fn
 
@@ -179,7 +180,8 @@ def _check_update(H, O, metric, shape, nupd, screen=1):
     s = _scenario(H, metric, nupd=nupd, screen=screen, **shape)
     g, ex0, ukeys, V = s["g"], s["ex0"], s["ukeys"], s["V"]
     _invariants(ex0, caps)
-    before = _edge_violations(H, metric, ex0, g.export_edge_dist())
+    before_d = g.export_edge_dist()
+    before = _edge_violations(H, metric, ex0, before_d)
     assert before == set(), sorted(before)[:5]
     state0 = (g.Len(), g.get_option("capacity"), g.get_option("dead_rows"), [f.count() for f in s["filters"]],
               g.preview_levels(16).tolist())
@@ -204,11 +206,25 @@ def _check_update(H, O, metric, shape, nupd, screen=1):
                       g.preview_levels(16).tolist())
     # 2: invariants and edge distances
     _invariants(ex1, caps)
-    after = _edge_violations(H, metric, ex1, g.export_edge_dist())
+    after_d = g.export_edge_dist()
+    after = _edge_violations(H, metric, ex1, after_d)
     assert after == set(), sorted(after)[:5]
     # 3: replay
     Q = np.concatenate([s["Q"], V[found]])
     _replay(H, O, g, ex1, Q, metric, M, m0, own=(ukeys[found], V[found]))
+    # 4: the restatement (og_add_batch, delete mode 1, og_update) given the same calls builds the
+    # same graph before and after the update: every field, adj in stored order, edge distance bits
+    opts = dict(ef_construction=shape["efc"], heuristic=2, keep_pruned=1)
+    o = O.Graph(metric=metric, order=O.ORDER_DEV, M=M, M0=m0, Ml=0.25, EfSearch=64)
+    cn = o.add_batch(s["keys"], s["X"], BR.levels_of(ex0), **opts)
+    assert all(o.delete(s["keys"][s["dead_rows"]], mode=1, heuristic=2, keep_pruned=1))
+    BR.same_export(ex0, o.export(), before_d, o.export_edge_dist(), what="before the update")
+    ofound, ucn = o.update(ukeys, V, **opts)
+    assert ofound.tolist() == found.tolist()
+    assert cn["dropped_proposals"] == 0 and ucn["dropped_proposals"] == 0
+    assert ucn["update_chunks"] == g.get_option("last_update_chunks")
+    assert ucn["repaired"] == g.get_option("last_update_repaired")
+    BR.same_export(ex1, o.export(), after_d, o.export_edge_dist(), what="after the update")
     return s, ex1, urows
 
 
