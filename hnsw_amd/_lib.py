@@ -57,6 +57,10 @@ SIGNATURES = {
     "mhnsw_range_results": (C.c_int, [_vp, _i64p, _f32p, C.c_int64]),
     "mhnsw_range_search_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, C.c_int64, _vp, _vp,
                                             _vp, _vp]),
+    "mhnsw_range_search_filtered": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _i32p,
+                                              _i64p]),
+    "mhnsw_range_search_filtered_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
+                                                     C.c_int, C.c_int64, _vp, _vp, _vp, _vp]),
     "mhnsw_search_negatives": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, _f32p, _i32p, C.c_int, C.c_float, C.c_int,
                                          C.c_int, C.c_int, _i64p, _f32p, _i32p]),
     "mhnsw_len": (C.c_int64, [_vp]),

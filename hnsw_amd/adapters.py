@@ -90,14 +90,17 @@ class ExactIndex:
         ok, od, on = self._g.search_filtered_arrays(np.asarray(queries, np.float32), k, filters, mode=MODE_EXACT)
         return [self._g.decode_keys(ok[b, : on[b]]) for b in range(len(on))], od, on
 
-    def RangeSearch(self, query, radius: float, mode: int = MODE_EXACT, ef: int = 0) -> List[Node]:
-        """Every key within `radius` of the query (Graph.RangeSearch), nearest first.  A flat
-        index answers in MODE_EXACT only: MODE_BEAM fails as a beam search does here."""
-        return self._g.RangeSearch(np.asarray(query, np.float32), radius, mode=mode, ef=ef)
+    def RangeSearch(self, query, radius: float, mode: int = MODE_EXACT, ef: int = 0, filter=None) -> List[Node]:
+        """Every key within `radius` of the query (Graph.RangeSearch), nearest first; with a
+        filter, every such key among the filter's.  A flat index answers in MODE_EXACT only:
+        MODE_BEAM fails as a beam search does here."""
+        return self._g.RangeSearch(np.asarray(query, np.float32), radius, mode=mode, ef=ef, filter=filter)
 
-    def range_search_batch(self, queries, radius, mode: int = MODE_EXACT, ef: int = 0):
-        """Batched form -> (lims int64[B + 1], keys [lims[B]], distances float32[lims[B]])."""
-        lims, keys, dist = self._g.range_search_arrays(np.asarray(queries, np.float32), radius, mode=mode, ef=ef)
+    def range_search_batch(self, queries, radius, mode: int = MODE_EXACT, ef: int = 0, filters=None):
+        """Batched form (filters: one Filter, or one per query; None: every key)
+        -> (lims int64[B + 1], keys [lims[B]], distances float32[lims[B]])."""
+        lims, keys, dist = self._g.range_search_arrays(np.asarray(queries, np.float32), radius, mode=mode, ef=ef,
+                                                       filters=filters)
         return lims, self._g.decode_keys(keys), dist
 
     def Delete(self, key) -> bool:  # exact.go:112-124

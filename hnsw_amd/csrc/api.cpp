@@ -1171,6 +1171,8 @@ int mhnsw_create(int metric, int M, double ml, int ef_search, uint64_t seed, mhn
         hipEventCreate(&h->fxev[0]) != hipSuccess || hipEventCreate(&h->fxev[1]) != hipSuccess ||
         hipEventCreate(&h->fxev[2]) != hipSuccess || hipEventCreate(&h->fxev[3]) != hipSuccess ||
         hipEventCreate(&h->fxev[4]) != hipSuccess || hipEventCreate(&h->fxev[5]) != hipSuccess ||
+        hipEventCreate(&h->fxev[6]) != hipSuccess || hipEventCreate(&h->fxev[7]) != hipSuccess ||
+        hipEventCreate(&h->fxev[8]) != hipSuccess ||
         hipEventCreate(&h->gev1) != hipSuccess || hipEventCreateWithFlags(&h->scr_ev, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->meta_ev, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ord_ev, hipEventDisableTiming) != hipSuccess || hipMemset(h->d_stats, 0, 16 * sizeof(unsigned long long)) != hipSuccess) {
@@ -1286,6 +1288,9 @@ void mhnsw_destroy(mhnsw_index* h) {
     F(h->rstat.p);
     F(h->rlims.p);
     F(h->rkeys.p);
+    F(h->rgkeys.p);
+    F(h->rgdist.p);
+    F(h->rgoff.p);
     F(h->uids.p);
     F(h->d_repaired);
     for (auto e : h->uev) (void)hipEventDestroy(e);
@@ -1552,8 +1557,11 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
         int i = 0;
         while (i < 5 && n != std::string("last_fx_") + stage[i] + "_ns") ++i;
         float ms = 0.f;
-        if (i == 5 || !h->have_fx_timing || hipEventSynchronize(h->fxev[i + 1]) != hipSuccess ||
-            hipEventElapsedTime(&ms, h->fxev[i], h->fxev[i + 1]) != hipSuccess)
+        // (a filtered exact-mode range search leaves the first two, of its row set, in fxev[6..8])
+        const bool rs = !h->have_fx_timing && h->have_range_timing && h->have_rs_timing && i < 2;
+        const int e0 = rs ? 6 + i : i;
+        if (i == 5 || !(h->have_fx_timing || rs) || hipEventSynchronize(h->fxev[e0 + 1]) != hipSuccess ||
+            hipEventElapsedTime(&ms, h->fxev[e0], h->fxev[e0 + 1]) != hipSuccess)
             return MHNSW_EINVAL;
         *v = (int64_t)std::llround((double)ms * 1e6);
     }
@@ -1837,6 +1845,20 @@ int mhnsw_range_search_device(mhnsw_index* h, const float* d_queries, int64_t B,
     std::unique_lock<std::shared_mutex> lk(h->mu);
     return range_search_device_impl(h, d_queries, B, dim, d_radius, mode, ef, cap, d_lims, d_keys, d_dist,
                                     (hipStream_t)stream);
+}
+
+int mhnsw_range_search_filtered(mhnsw_index* h, const float* queries, int64_t B, int dim, const float* radius, int mode,
+                                int ef, int route, const int32_t* filter_of, int64_t* out_lims) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    return range_search_filtered_impl(h, queries, B, dim, radius, mode, ef, route, filter_of, out_lims);
+}
+
+int mhnsw_range_search_filtered_device(mhnsw_index* h, const float* d_queries, int64_t B, int dim, const float* d_radius,
+                                       int mode, int ef, int route, int filter, int64_t cap, int64_t* d_lims,
+                                       int64_t* d_keys, float* d_dist, void* stream) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    return range_search_filtered_device_impl(h, d_queries, B, dim, d_radius, mode, ef, route, filter, cap, d_lims, d_keys,
+                                             d_dist, (hipStream_t)stream);
 }
 
 // read-locked like the reference's Len/Dims (graph.go:421,829): a concurrent Add may grow h->layers

@@ -435,12 +435,17 @@ struct RangeArgs {
     unsigned long long* hits;  // [hcap] {order image of the distance, row id}
     int64_t hcap, cap;     // hit buffer entries; the caller's capacity (queries starting at or past it write nothing)
     unsigned long long* stat;  // [0] pairs that reached refine, [1] queries the sweep answered
+    // a filter's gathered row set (nullptr: every row of the index): the ascending ids of its m
+    // rows; a bucket entry is then a position in the set's plane, and the sweep walks the list
+    const uint32_t* ids;
+    int64_t m;
 };
 int launch_range_thr(const RangeArgs& a, const float* qnorm, const float* qinv, const CertArgs& c, int fused, float* thr,
                      hipStream_t s);
 int launch_range_refine(const RangeArgs& a, int lpr, int vpl, hipStream_t s);
 int launch_range_gather(const RangeArgs& a, hipStream_t s);
-// canonical sweep of rows [0, N) for the queries a.sweep flags: write = false counts, true writes
+// canonical sweep of rows [0, N) (of a row set: its N = a.m rows) for the queries a.sweep flags:
+// write = false counts, true writes
 int launch_range_sweep(const RangeArgs& a, int64_t N, int nseg, int64_t seglen, bool write, int lpr, int vpl,
                        hipStream_t s);
 int launch_range_scan(const int32_t* cnt, int64_t B, int64_t* lims, int32_t* cursor, hipStream_t s);
@@ -448,6 +453,9 @@ int range_sort_temp_bytes(int64_t hcap, int64_t B, size_t* bytes);
 int launch_range_order_emit(const unsigned long long* hits, unsigned long long* sorted, int64_t hcap,
                             const int64_t* lims, int64_t B, int64_t cap, uint32_t* seg_b, uint32_t* seg_e, void* temp,
                             size_t temp_bytes, const GraphDev& g, int64_t* keys, float* dist, hipStream_t s);
+// src_keys / src_dist [src_off[b] ..) -> keys / dist [lims[b], lims[b + 1]), one block per query
+int launch_range_place(const int64_t* src_keys, const float* src_dist, const int64_t* src_off, const int64_t* lims,
+                       int64_t B, int64_t* keys, float* dist, hipStream_t s);
 // beam mode: the beam lists bk / bd / bn [B * ef] cut by the radius -> lims, keys, dist
 int launch_range_beam(const int64_t* bk, const float* bd, const int32_t* bn, int ef, const float* radius, int64_t B,
                       int32_t* cnt, int64_t* lims, int64_t cap, int64_t* keys, float* dist, hipStream_t s);

@@ -249,8 +249,10 @@ struct mhnsw_index {
     DevBuf<float> fxinv, fxnorm;
     // stage marks of the last filtered exact search: start, compaction done, gather done, and
     // around the first query chunk's re-rank and fallback (options "last_fx_*_ns")
-    hipEvent_t fxev[6] = {};
+    // ([6..8]: a filtered exact-mode range search's row set -- start, compaction done, gather done)
+    hipEvent_t fxev[9] = {};
     bool have_fx_timing = false;
+    bool have_rs_timing = false;
     // range search (range.hip): per-chunk thresholds, query states and counts, the call's hit
     // buffer (unsorted and sorted halves), sort segments and temporary storage, the counters of
     // the last call, and a host-pointer call's radii, prefix and results (mhnsw_range_results)
@@ -262,6 +264,9 @@ struct mhnsw_index {
     DevBuf<uint32_t> rseg;
     DevBuf<unsigned long long> rhits, rstat;
     DevBuf<int64_t> rlims, rkeys;
+    // a host filtered range search of several filters: the passes' hits, and each query's offset in them
+    DevBuf<int64_t> rgkeys, rgoff;
+    DevBuf<float> rgdist;
     int64_t range_total = -1;  // hits the last host-pointer range search left in rkeys / rdist (-1: none)
     bool have_range_stats = false;
     bool have_range_timing = false;  // fxev holds an exact-mode range search's stage marks (options "last_range_*_ns")
@@ -345,6 +350,8 @@ int search_filtered_impl(mhnsw_index* h, const float* queries, bool on_device, i
 int search_filtered_exact_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int filter, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool sticky);
 int range_search_impl(mhnsw_index* h, const float* queries, int64_t B, int dim, const float* radius, int mode, int ef, int64_t* out_lims);
 int range_search_device_impl(mhnsw_index* h, const float* d_queries, int64_t B, int dim, const float* d_radius, int mode, int ef, int64_t cap, int64_t* d_lims, int64_t* d_keys, float* d_dist, hipStream_t s);
+int range_search_filtered_impl(mhnsw_index* h, const float* queries, int64_t B, int dim, const float* radius, int mode, int ef, int route, const int32_t* filter_of, int64_t* out_lims);
+int range_search_filtered_device_impl(mhnsw_index* h, const float* d_queries, int64_t B, int dim, const float* d_radius, int mode, int ef, int route, int filter, int64_t cap, int64_t* d_lims, int64_t* d_keys, float* d_dist, hipStream_t s);
 int import_csr(mhnsw_index* h, int64_t N, int dim, int L, int cap, const int64_t* keys, const float* vecs, const int32_t* deg, const int32_t* adj, const int32_t* entry, const uint8_t* dead);
 const char* metric_name(int m);
 int strkey_relabel(mhnsw_index* h);

@@ -10,6 +10,8 @@
 //                   sub-bucket; a query whose region or sub-bucket overflowed goes to the sweep.
 //  k_range_sweep  : canonical distances of every row for the queries the filter cannot cover
 //                   (k_exact_fallback's arithmetic), once to count and once to write.
+//  (SET: the rows are a filter's gathered row set -- a candidate is a position in the set's
+//   plane, mapped through the ascending id list as it is loaded, and the sweep walks the list.)
 //  k_range_scan   : the chunk's counts -> lims (exclusive prefix, carried over the chunks).
 //  k_range_gather : a fused query's hits from its sub-buckets to its segment of the hit buffer.
 //  k_range_segs + rocPRIM's segmented radix sort: each query's segment by (distance, row id);
@@ -90,7 +92,7 @@ __global__ void k_range_thr(RangeArgs a, const float* __restrict__ qnorm, const 
     a.sweep[b] = st == 1;
 }
 
-template <class C, int G>
+template <class C, int G, bool SET>
 __global__ __launch_bounds__(256) void k_range_refine(RangeArgs a) {
     const int64_t b = blockIdx.x;
     if (b >= a.B || a.state[b] != 0) return;
@@ -113,9 +115,11 @@ __global__ __launch_bounds__(256) void k_range_refine(RangeArgs a) {
         int out = 0;
         for (int base = 0; base < n; base += 64) {
             const int e = base + lane;
-            const uint32_t row = e < n ? bk[e].x : EMPTY_ID;
+            uint32_t row = e < n ? bk[e].x : EMPTY_ID;
+            // (positions ascend with the row ids: the order of the hits downstream is the same)
+            if constexpr (SET) row = row < (uint32_t)a.m ? a.ids[row] : EMPTY_ID;
             int cnt;
-            const uint32_t cid = compact(row, e < n, cnt);
+            const uint32_t cid = compact(row, SET ? row != EMPTY_ID : e < n, cnt);
             float myd = __int_as_float(0x7f800000);
             int j = 0;
             eval_list<C, G>(a.g, q, qn, cid, cnt, a.g.metric, [&](float d, uint32_t) {
@@ -161,7 +165,9 @@ __global__ __launch_bounds__(64) void k_range_gather(RangeArgs a) {
 // Block (b, s): query b (sweep[b] set, else it exits at once), row segment s; its 4 waves take
 // a quarter of the segment each.  WRITE = false counts the hits, WRITE = true writes them at
 // the query's cursor: per 64-row step one integer atomic per wave that has a hit.
-template <class C, int G, bool WRITE>
+// SET: N is the row set's size and a "row" below a position of its id list -- the rows read
+// are a.ids[position], none of them skipped (the list holds no deleted row).
+template <class C, int G, bool WRITE, bool SET>
 __global__ __launch_bounds__(256) void k_range_sweep(RangeArgs a, int64_t N, int nseg, int64_t seglen) {
     using RM = RowMap<C, G>;
     constexpr int GROUP = C::LPR >> RM::LG;
@@ -188,17 +194,23 @@ __global__ __launch_bounds__(256) void k_range_sweep(RangeArgs a, int64_t N, int
         for (int gg = 0; gg < G; ++gg) {
             const int64_t rr = base + RM::reg_row(gg, lane);
             valid[gg] = rr < whi;
-            ids[gg] = valid[gg] ? (uint32_t)rr : 0u;
+            if constexpr (SET)
+                ids[gg] = valid[gg] ? a.ids[rr] : 0u;
+            else
+                ids[gg] = valid[gg] ? (uint32_t)rr : 0u;
         }
         const float sacc = g.metric == EUCLIDEAN ? eval_rows<C, G, true>(q, g.vecs, g.pitch, ids, valid)
                                                  : eval_rows<C, G, false>(q, g.vecs, g.pitch, ids, valid);
         const int64_t rown = base + RM::owned_row(lane);
         const bool own = rown < whi && (lane & (GROUP - 1)) == 0;
         float d = inf;
+        uint32_t rid = (uint32_t)rown;
         if (own) {
-            const float xn = g.metric == COSINE ? g.norms[rown] : 1.f;
+            if constexpr (SET) rid = a.ids[rown];
+            const float xn = g.metric == COSINE ? g.norms[rid] : 1.f;
             d = finalize(g.metric, sacc, xn, qn);
-            if (g.dead && g.dead[rown]) d = inf;
+            if constexpr (!SET)
+                if (g.dead && g.dead[rown]) d = inf;
         }
         const bool hit = own && range_hit(d, r);
         const unsigned long long m = __ballot(hit);
@@ -210,7 +222,7 @@ __global__ __launch_bounds__(256) void k_range_sweep(RangeArgs a, int64_t N, int
             at = uni(at);
             const int before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
             const int64_t slot = qbase + at + before;
-            if (hit && slot < a.hcap) a.hits[slot] = range_key(d, (uint32_t)rown);
+            if (hit && slot < a.hcap) a.hits[slot] = range_key(d, rid);
         } else {
             total += nh;
         }
@@ -316,6 +328,22 @@ __global__ __launch_bounds__(64) void k_range_emit_beam(const int64_t* __restric
     }
 }
 
+// A host batch of several filters: query b's sorted hits, left at src_off[b] of the staging
+// buffers by its filter's pass, to its own segment [lims[b], lims[b + 1]) of the result.
+__global__ __launch_bounds__(256) void k_range_place(const int64_t* __restrict__ src_keys,
+                                                     const float* __restrict__ src_dist,
+                                                     const int64_t* __restrict__ src_off,
+                                                     const int64_t* __restrict__ lims, int64_t B,
+                                                     int64_t* __restrict__ keys, float* __restrict__ dist) {
+    const int64_t b = blockIdx.x;
+    if (b >= B) return;
+    const int64_t from = src_off[b], to = lims[b], n = lims[b + 1] - to;
+    for (int64_t e = threadIdx.x; e < n; e += 256) {
+        keys[to + e] = src_keys[from + e];
+        dist[to + e] = src_dist[from + e];
+    }
+}
+
 // ---------------------------------------------------------------------------
 int launch_range_thr(const RangeArgs& a, const float* qnorm, const float* qinv, const CertArgs& c, int fused, float* thr,
                      hipStream_t s) {
@@ -327,7 +355,10 @@ int launch_range_thr(const RangeArgs& a, const float* qnorm, const float* qinv, 
 int launch_range_refine(const RangeArgs& a, int lpr, int vpl, hipStream_t s) {
     if (a.B <= 0) return 0;
     return with_cfg(lpr, vpl, [&](auto cfg) {
-        hipLaunchKernelGGL((k_range_refine<Cfg<cfg.L, cfg.V>, cfg.G>), dim3((unsigned)a.B), dim3(256), 0, s, a);
+        if (a.ids)
+            hipLaunchKernelGGL((k_range_refine<Cfg<cfg.L, cfg.V>, cfg.G, true>), dim3((unsigned)a.B), dim3(256), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_range_refine<Cfg<cfg.L, cfg.V>, cfg.G, false>), dim3((unsigned)a.B), dim3(256), 0, s, a);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     });
 }
@@ -341,15 +372,19 @@ int launch_range_gather(const RangeArgs& a, hipStream_t s) {
 int launch_range_sweep(const RangeArgs& a, int64_t N, int nseg, int64_t seglen, bool write, int lpr, int vpl,
                        hipStream_t s) {
     if (a.B <= 0 || N <= 0) return 0;
-    if (nseg < 1 || seglen < 1) return -4;
+    if (nseg < 1 || seglen < 1 || (a.ids && N != a.m)) return -4;
     const dim3 grid((unsigned)(a.B * nseg));
     return with_cfg(lpr, vpl, [&](auto c) {
         using C = Cfg<c.L, c.V>;
         constexpr int GF = c.G < 4 ? c.G : 4;
-        if (write)
-            hipLaunchKernelGGL((k_range_sweep<C, GF, true>), grid, dim3(256), 0, s, a, N, nseg, seglen);
+        if (a.ids && write)
+            hipLaunchKernelGGL((k_range_sweep<C, GF, true, true>), grid, dim3(256), 0, s, a, N, nseg, seglen);
+        else if (a.ids)
+            hipLaunchKernelGGL((k_range_sweep<C, GF, false, true>), grid, dim3(256), 0, s, a, N, nseg, seglen);
+        else if (write)
+            hipLaunchKernelGGL((k_range_sweep<C, GF, true, false>), grid, dim3(256), 0, s, a, N, nseg, seglen);
         else
-            hipLaunchKernelGGL((k_range_sweep<C, GF, false>), grid, dim3(256), 0, s, a, N, nseg, seglen);
+            hipLaunchKernelGGL((k_range_sweep<C, GF, false, false>), grid, dim3(256), 0, s, a, N, nseg, seglen);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     });
 }
@@ -382,6 +417,14 @@ int launch_range_order_emit(const unsigned long long* hits, unsigned long long* 
     if (cap <= 0) return 0;
     const int64_t blocks = std::min<int64_t>((cap + 255) / 256, 8192);
     hipLaunchKernelGGL(k_range_emit, dim3((unsigned)blocks), dim3(256), 0, s, sorted, lims + B, cap, g.keys, g.capn, keys,
+                       dist);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_range_place(const int64_t* src_keys, const float* src_dist, const int64_t* src_off, const int64_t* lims,
+                       int64_t B, int64_t* keys, float* dist, hipStream_t s) {
+    if (B <= 0) return 0;
+    hipLaunchKernelGGL(k_range_place, dim3((unsigned)B), dim3(256), 0, s, src_keys, src_dist, src_off, lims, B, keys,
                        dist);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

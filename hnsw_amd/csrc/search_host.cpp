@@ -7,6 +7,8 @@
 // fused preselection, bucket select, canonical re-rank, certificate, fallback), beam_search
 // or compat_search.  exact_prepare / exact_run work on a RowSet: every row of the index, or
 // (search_filtered_exact) a filter's allowed rows gathered into a dense plane (rowset.hip).
+// The range search (range_search, range_exact) runs over the same two kinds of row set, and in
+// beam mode cuts the beam search's or the filtered walk's (filtered_walk) lists.
 // Last, the negative-example re-ranking.
 #include "index.hpp"
 
@@ -386,8 +388,12 @@ static int exact_prepare(mhnsw_index* h, const SearchCall& c, const RowSet& rs, 
     const int rsub = h1_region_split(ev);
     // (a range search: 8x the expected hits, at least 128 per sub-bucket -- a query that passes
     // more is answered by the sweep, so the floor only has to cover what the radius lets through)
+    // (a row tile goes to sub-bucket tile % H1_BSUB: a small index, or a selective filter's row
+    // set, of fewer tiles than that uses only so many sub-buckets, and the range search spreads
+    // its 8x over the ones in use)
+    const int64_t subs = expect > 0 ? std::min<int64_t>(H1_BSUB, std::max<int64_t>(nnt, 1)) : H1_BSUB;
     const int scap = (int)std::min<int64_t>(std::max<int64_t>(N, 1),
-                                            std::max<int64_t>(expect > 0 ? 128 : 512, 8 * Jc * N / ns / H1_BSUB));
+                                            std::max<int64_t>(expect > 0 ? 128 : 512, 8 * Jc * N / ns / subs));
     if (h1 && ((r = ensure_buf(h, h->h1thr, (size_t)qc)) || (r = ensure_buf(h, h->h1c, (size_t)nqt * bm + 256)) ||
                (r = ensure_buf(h, h->h1s, (size_t)nqt * bm + 256)) ||
                (r = ensure_buf(h, h->h1region, (size_t)nqt * nnt * rcap)) ||
@@ -656,6 +662,37 @@ static int search_plain(mhnsw_index* h, SearchCall& c, int mode, int ef, const i
     return r ? r : finish(h, c);
 }
 
+// The filtered walk's launch on c.s, for the filtered search and the filtered range search's
+// beam mode: lists of the E best allowed rows per query (to c's outputs, staged here) through
+// an LDS route list of W entries.  filter_of: a host array of checked ids (it is uploaded), or
+// for a device call the device's.  timed: the walk's event pair is recorded.
+static int filtered_walk(mhnsw_index* h, SearchCall& c, int E, int W, const int32_t* filter_of, bool timed) {
+    int r;
+    // a bitmap that has to grow with the rows moves: nothing enqueued may read it
+    const size_t words = (size_t)((h->capn + 31) / 32);
+    const auto grows = [&](const mhnsw_index::Filter& F) { return F.used && F.bits.size() < words; };
+    if (std::any_of(h->filters.begin(), h->filters.end(), grows) && (r = drain(h))) return r;
+    if ((r = filters_fit(h))) return r;
+    const int top = top_live_layer(h);
+    if (!c.on_device) {  // (the filtered call's own upload, next to stage()'s of the queries)
+        if ((r = ensure_buf(h, h->fof, (size_t)c.B))) return r;
+        HIPCHK(h, hipMemcpyAsync(h->fof.p, filter_of, (size_t)c.B * 4, hipMemcpyHostToDevice, c.s));
+    }
+    const FilterArgs f{h->d_filters, MHNSW_MAX_FILTERS, E, c.on_device ? filter_of : h->fof.p};
+    if ((r = stage(h, c))) return r;
+    SearchArgs a;  // (ef: the route list's width W, in LDS; FilterArgs::ef is the result list's)
+    if ((r = walk_args(h, c, top, (uint32_t)h->layers[top].entry, W, true, a))) return r;
+    a.mw_max_b = 0;
+    a.expand = 1;
+    if (timed) HIPCHK(h, hipEventRecord(h->ev0, c.s));
+    const int lr = launch_search_beam_filtered(a, f, h->lpr, h->vpl, c.s);
+    if (lr == -2)
+        return fail(h, MHNSW_EUNSUPPORTED, "filtered search LDS budget exceeded (route=%d, vis_entries=%d)", W, a.vis_n);
+    LCHK(h, lr);
+    if (timed) HIPCHK(h, hipEventRecord(h->ev1, c.s));
+    return 0;
+}
+
 // The filtered beam search (beam.hpp k_search_beam_filt): the fused launch over the LDS list of `route`
 // entries, results from the list of max(ef, k) allowed rows.  Always timed (c.timing is set).
 static int search_filtered(mhnsw_index* h, SearchCall& c, int ef, int route, const int32_t* filter_of) {
@@ -676,52 +713,24 @@ static int search_filtered(mhnsw_index* h, SearchCall& c, int ef, int route, con
                 return fail(h, MHNSW_EINVAL, "unknown filter %d", f);
         }
     if (!h->layers_exist || live_count(h) == 0) return zero_counts(h, c);
-    // a bitmap that has to grow with the rows moves: nothing enqueued may read it
-    const size_t words = (size_t)((h->capn + 31) / 32);
-    const auto grows = [&](const mhnsw_index::Filter& F) { return F.used && F.bits.size() < words; };
-    if (std::any_of(h->filters.begin(), h->filters.end(), grows) && (r = drain(h))) return r;
-    if ((r = filters_fit(h))) return r;
-    const int top = top_live_layer(h);
-    if (!c.on_device) {  // (the filtered call's own upload, next to stage()'s of the queries)
-        if ((r = ensure_buf(h, h->fof, (size_t)c.B))) return r;
-        HIPCHK(h, hipMemcpyAsync(h->fof.p, filter_of, (size_t)c.B * 4, hipMemcpyHostToDevice, c.s));
-    }
-    const FilterArgs f{h->d_filters, MHNSW_MAX_FILTERS, E, c.on_device ? filter_of : h->fof.p};
-    if ((r = stage(h, c))) return r;
-    SearchArgs a;  // (ef: the route list's width W, in LDS; FilterArgs::ef is the result list's)
-    if ((r = walk_args(h, c, top, (uint32_t)h->layers[top].entry, W, true, a))) return r;
-    a.mw_max_b = 0;
-    a.expand = 1;
-    HIPCHK(h, hipEventRecord(h->ev0, c.s));
-    const int lr = launch_search_beam_filtered(a, f, h->lpr, h->vpl, c.s);
-    if (lr == -2)
-        return fail(h, MHNSW_EUNSUPPORTED, "filtered search LDS budget exceeded (route=%d, vis_entries=%d)", W, a.vis_n);
-    LCHK(h, lr);
-    HIPCHK(h, hipEventRecord(h->ev1, c.s));
+    if ((r = filtered_walk(h, c, E, W, filter_of, true))) return r;
     h->have_gemm_timing = false;
     return finish(h, c);
 }
 
-// The filtered exact search of one filter (>= 0): the exact pipeline over the filter's allowed
-// rows as a gathered row set.  The host's mirror of the bitmap sizes the launches (the same
-// words and skipped rows the compaction kernel counts).  Always timed, with stage marks.
-static int search_filtered_exact(mhnsw_index* h, SearchCall& c, int filter) {
-    int r = validate(h);
-    if (r || (r = check_args(h, c, MHNSW_MODE_EXACT))) return r;
-    if (c.k > 256) return fail(h, MHNSW_EUNSUPPORTED, "exact mode supports k <= 256");
-    if (filter < 0 || filter >= (int)h->filters.size() || !h->filters[filter].used)
-        return fail(h, MHNSW_EINVAL, "unknown filter %d", filter);
-    if (c.B <= 0) return 0;
-    h->have_gemm_timing = false;
-    h->have_fx_timing = false;
-    if (!h->layers_exist || live_count(h) == 0) return zero_counts(h, c);
+// The allowed rows of filter (a used slot) as a gathered row set, for the filtered exact search
+// and the filtered range search: the host's count of them, the set's buffers sized for it, ids
+// pointing at the list launch_rowset_compact fills.  rs.n == 0: nothing is allowed, and no
+// buffer was touched.
+static int filter_rowset(mhnsw_index* h, hipStream_t s, int filter, int precision, RowSet& rs) {
+    int r;
     // a bitmap that has to grow with the rows moves: nothing enqueued may read it
     const size_t words = (size_t)((h->capn + 31) / 32);
     const auto grows = [&](const mhnsw_index::Filter& F) { return F.used && F.bits.size() < words; };
     if (std::any_of(h->filters.begin(), h->filters.end(), grows) && (r = drain(h))) return r;
     if ((r = filters_fit(h))) return r;
     const uint8_t* xdead;
-    if ((r = exact_skipped(h, c.s, xdead))) return r;
+    if ((r = exact_skipped(h, s, xdead))) return r;
     const mhnsw_index::Filter& F = h->filters[filter];
     const int64_t nwords = (h->n + 31) / 32, fwords = std::min<int64_t>(nwords, (int64_t)F.bits.size());
     int64_t m = 0;
@@ -737,20 +746,38 @@ static int search_filtered_exact(mhnsw_index* h, SearchCall& c, int filter) {
             m += !h->hdead[(size_t)i] && (!h->partial_rows || in_layer(h, i, 0));
         }
     }
-    if (m == 0) {  // nothing allowed: no row, no error
-        h->stats_host[6] += c.B;
-        h->have_timing = false;
-        return zero_counts(h, c);
-    }
-    // without an fp16 row plane (exact_precision 0 or 1) the call scores at precision 3
-    const RowSet rs{m, (m + 255) / 256 * 256, h->exact_precision >= 2 ? h->exact_precision : 3, nullptr, F.d, fwords};
+    rs = RowSet{m, (m + 255) / 256 * 256, precision, nullptr, F.d, fwords};
+    if (m == 0) return 0;
     if ((r = ensure_buf(h, h->fxwords, (size_t)nwords)) || (r = ensure_buf(h, h->fxmask, (size_t)nwords * 32)) ||
         (r = ensure_buf(h, h->fxcnt, (size_t)rowset_blocks(h->n))) || (r = ensure_buf(h, h->fxids, (size_t)m)) ||
         (r = ensure_buf(h, h->fxplane, (size_t)rs.ld * h->pitch)) || (r = ensure_buf(h, h->fxinv, (size_t)rs.ld)) ||
         (r = ensure_buf(h, h->fxnorm, (size_t)rs.ld)))
         return r;
-    RowSet rset = rs;
-    rset.ids = h->fxids.p;
+    rs.ids = h->fxids.p;
+    return 0;
+}
+
+// The filtered exact search of one filter (>= 0): the exact pipeline over the filter's allowed
+// rows as a gathered row set.  The host's mirror of the bitmap sizes the launches (the same
+// words and skipped rows the compaction kernel counts).  Always timed, with stage marks.
+static int search_filtered_exact(mhnsw_index* h, SearchCall& c, int filter) {
+    int r = validate(h);
+    if (r || (r = check_args(h, c, MHNSW_MODE_EXACT))) return r;
+    if (c.k > 256) return fail(h, MHNSW_EUNSUPPORTED, "exact mode supports k <= 256");
+    if (filter < 0 || filter >= (int)h->filters.size() || !h->filters[filter].used)
+        return fail(h, MHNSW_EINVAL, "unknown filter %d", filter);
+    if (c.B <= 0) return 0;
+    h->have_gemm_timing = false;
+    h->have_fx_timing = false;
+    if (!h->layers_exist || live_count(h) == 0) return zero_counts(h, c);
+    // without an fp16 row plane (exact_precision 0 or 1) the call scores at precision 3
+    RowSet rset;
+    if ((r = filter_rowset(h, c.s, filter, h->exact_precision >= 2 ? h->exact_precision : 3, rset))) return r;
+    if (rset.n == 0) {  // nothing allowed: no row, no error
+        h->stats_host[6] += c.B;
+        h->have_timing = false;
+        return zero_counts(h, c);
+    }
     if ((r = stage(h, c))) return r;
     ExactPlan plan;
     if (!(r = exact_prepare(h, c, rset, plan))) r = exact_run(h, c, plan);
@@ -789,17 +816,31 @@ struct RangeOut {
     int64_t* keys;
     float* dist;
 };
+// The rows a range search is over.  Exact mode: one filter for the call (-1: every live row).
+// Beam mode: walk set, the filtered walk through a route list, a filter per query in filter_of
+// (a host array, or for a device call nullptr: `filter` for every query).
+struct RangeRows {
+    int filter = -1;
+    bool walk = false;
+    int route = 0;
+    const int32_t* filter_of = nullptr;
+};
 
 // Exact mode.  Per chunk of queries: the radius as the filter GEMM's threshold, the filter and
 // the buckets as exact_run runs them, the canonical refine of the candidates, the sweep for the
 // queries the filter does not cover; counts, then the chunk's part of lims, then the writes.
 // Once per call: each query's segment of the hit buffer sorted, keys and distances emitted.
+// The plan's row set is every row of the index, or a filter's allowed rows: then the id list
+// is compacted and the rows' plane gathered first (as exact_run does), the GEMM runs over the
+// gathered plane, refine maps its positions to row ids and the sweep walks the id list.
 static int range_exact(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan, const RangeOut& o) {
     int r;
     hipStream_t s = c.s;
+    const RowSet& rs = plan.rs;
+    const bool gathered = rs.ids != nullptr;
     const bool fused = plan.h1 && !h->range_force_fallback;
     const int64_t qc = plan.qc, B = c.B;
-    const int64_t hcap = o.cap + h->n;  // a query that starts below cap holds all its hits (<= n)
+    const int64_t hcap = o.cap + rs.n;  // a query that starts below cap holds all its hits (<= the set's rows)
     if (hcap > (int64_t)0x7fffffff)
         return fail(h, MHNSW_EUNSUPPORTED, "range search supports cap + rows < 2^31");
     size_t tmp_bytes = 0;
@@ -815,6 +856,31 @@ static int range_exact(mhnsw_index* h, const SearchCall& c, const ExactPlan& pla
                                  h->xerr.p, s));
         h->xsplit_rows = h->n;
     }
+    // the set's plane and per-row constants: the handle's, or the allowed rows' gathered from
+    // them (xerr, and below the L2 xmax, stay maxima over every row: bounds that hold for a subset)
+    const uint16_t* Xh = h->xsplit.p;
+    int64_t ldX = h->capn;
+    const float* xinv = h->xinv.p;
+    const float* xnorm = h->norms;
+    const uint8_t* sdead = plan.xdead;
+    if (gathered) {
+        const bool marks = c.timing;  // options last_fx_compact_ns / last_fx_gather_ns
+        if (marks) HIPCHK(h, hipEventRecord(h->fxev[6], s));
+        LCHK(h, launch_rowset_compact(rs.filter, rs.fwords, plan.xdead, h->n, h->fxwords.p, h->fxmask.p, h->fxcnt.p,
+                                      h->fxids.p, rs.n, s));
+        if (marks) HIPCHK(h, hipEventRecord(h->fxev[7], s));
+        if (fused) {  // (a swept search reads the f32 rows through the id list: no plane)
+            LCHK(h, launch_rowset_gather(h->xsplit.p, h->capn, rs.ids, rs.n, h->pitch, h->fxplane.p, rs.ld, h->xinv.p,
+                                         h->norms, h->fxinv.p, h->fxnorm.p, s));
+            Xh = h->fxplane.p;
+            ldX = rs.ld;
+            xinv = h->fxinv.p;
+            xnorm = h->fxnorm.p;
+            sdead = nullptr;
+        }
+        if (marks) HIPCHK(h, hipEventRecord(h->fxev[8], s));
+        h->have_rs_timing = marks;
+    }
     if (h->metric == EUCLIDEAN) {
         HIPCHK(h, hipMemsetAsync(h->xmaxn.p, 0, sizeof(float), s));
         LCHK(h, launch_max_norm(h->norms, h->n, h->xmaxn.p, s));
@@ -822,6 +888,8 @@ static int range_exact(mhnsw_index* h, const SearchCall& c, const ExactPlan& pla
     for (int64_t q0 = 0; q0 < B; q0 += qc) {
         const int64_t nb = std::min(qc, B - q0);
         RangeArgs ra{};
+        ra.ids = rs.ids;
+        ra.m = rs.n;
         ra.g = plan.g;
         ra.Q = h->qpad.p + (size_t)q0 * h->pitch;
         ra.radius = o.radius + q0;
@@ -854,22 +922,22 @@ static int range_exact(mhnsw_index* h, const SearchCall& c, const ExactPlan& pla
             // 2. the filter GEMM and the per-query buckets, as the top-k search runs them
             ExactArgs a{};
             a.X = h->vecs;
-            a.xnorm = h->norms;
-            a.dead = plan.xdead;
-            a.N = h->n;
+            a.xnorm = xnorm;
+            a.dead = sdead;
+            a.N = rs.n;
             a.Q = ra.Q;
             a.qnorm = c1.qnorm;
             a.B = nb;
             a.pitch = h->pitch;
             a.dim = h->dim;
             a.metric = h->metric;
-            a.Xh = h->xsplit.p;
-            a.Xl = h->xsplit.p + (size_t)h->capn * h->pitch;
-            a.ldXs = h->capn;
+            a.Xh = Xh;
+            a.Xl = Xh + (size_t)ldX * h->pitch;
+            a.ldXs = ldX;
             a.Qh = h->qsplit.p;
             a.Ql = h->qsplit.p + (size_t)qc * h->pitch;
             a.ldQs = qc;
-            a.xinv = h->xinv.p;
+            a.xinv = xinv;
             a.qinv = h->qinv.p;
             LCHK(h, launch_ring_prep(h->rthr.p, a.qnorm, a.qinv, nb, h->metric, h->h1c.p, h->h1s.p, s));
             HIPCHK(h, hipMemsetAsync(h->h1qcnt.p, 0, (size_t)nb * H1_BSUB * H1_CSTRIDE * 4, s));
@@ -901,10 +969,10 @@ static int range_exact(mhnsw_index* h, const SearchCall& c, const ExactPlan& pla
         }
         if (mark0) HIPCHK(h, hipEventRecord(h->fxev[2], s));
         // 4. the sweep's count, the chunk's prefix, then the writes into the queries' segments
-        LCHK(h, launch_range_sweep(ra, h->n, plan.nseg, plan.seglen, false, h->lpr, h->vpl, s));
+        LCHK(h, launch_range_sweep(ra, rs.n, plan.nseg, plan.seglen, false, h->lpr, h->vpl, s));
         LCHK(h, launch_range_scan(h->rcnt.p, nb, ra.lims, h->rcursor.p, s));
         if (fused) LCHK(h, launch_range_gather(ra, s));
-        LCHK(h, launch_range_sweep(ra, h->n, plan.nseg, plan.seglen, true, h->lpr, h->vpl, s));
+        LCHK(h, launch_range_sweep(ra, rs.n, plan.nseg, plan.seglen, true, h->lpr, h->vpl, s));
         if (mark0) HIPCHK(h, hipEventRecord(h->fxev[3], s));
     }
     if (c.timing) HIPCHK(h, hipEventRecord(h->fxev[4], s));
@@ -920,20 +988,34 @@ static int range_exact(mhnsw_index* h, const SearchCall& c, const ExactPlan& pla
 
 // The kernels of one range search, enqueued on c.s.  c.k is set here: 1 in exact mode (the
 // exact path's workspace sizing), ef in beam mode (the beam search's list).
-static int range_search(mhnsw_index* h, SearchCall& c, int mode, int ef, const RangeOut& o) {
+static int range_search(mhnsw_index* h, SearchCall& c, int mode, int ef, const RangeOut& o,
+                        const RangeRows& rows = RangeRows()) {
     int r = validate(h);
     if (r) return r;
     h->have_gemm_timing = false;
     h->have_range_stats = false;
     h->have_range_timing = false;
+    h->have_rs_timing = false;
     h->have_fx_timing = false;  // (the stage events are shared with the filtered exact search)
     c.k = 1;
     if ((r = check_args(h, c, mode))) return r;
     if (mode == MHNSW_MODE_COMPAT) return fail(h, MHNSW_EUNSUPPORTED, "range search supports beam and exact mode");
     if (o.cap < 0) return fail(h, MHNSW_EINVAL, "cap must be >= 0, got %lld", (long long)o.cap);
     if (ef <= 0) ef = h->ef;
+    const bool walk = rows.walk && mode == MHNSW_MODE_BEAM;
+    int W = 0;
+    if (walk) {  // the filtered walk's limits, in its words
+        if (std::max(ef, 1) > 128) return fail(h, MHNSW_EUNSUPPORTED, "filtered search supports max(ef,k) <= 128");
+        W = std::max(rows.route > 0 ? rows.route : h->filter_route, std::max(ef, 1));
+        if (W > 2048) return fail(h, MHNSW_EUNSUPPORTED, "filtered search supports route <= 2048");  // (LL_MAX_EF)
+    }
     if (mode == MHNSW_MODE_BEAM && std::max(ef, 1) > 2048)
         return fail(h, MHNSW_EUNSUPPORTED, "beam mode supports max(ef,k) <= 2048");
+    const auto known = [&](int f) { return f == -1 || (f >= 0 && f < (int)h->filters.size() && h->filters[f].used); };
+    if (!known(rows.filter)) return fail(h, MHNSW_EINVAL, "unknown filter %d", rows.filter);
+    if (walk && rows.filter_of)
+        for (int64_t b = 0; b < c.B; ++b)
+            if (!known(rows.filter_of[b])) return fail(h, MHNSW_EINVAL, "unknown filter %d", rows.filter_of[b]);
     hipStream_t s = c.s;
     if (c.B <= 0 || !h->layers_exist || live_count(h) == 0) {  // no query or no row: all-zero lims
         HIPCHK(h, hipMemsetAsync(o.lims, 0, (size_t)(std::max<int64_t>(c.B, 0) + 1) * 8, s));
@@ -951,11 +1033,40 @@ static int range_search(mhnsw_index* h, SearchCall& c, int mode, int ef, const R
         // like the filtered exact search, the call always scores at precision 3 (its results do
         // not depend on the precision)
         ExactPlan plan;
-        const RowSet every{h->n, h->capn, 3, nullptr, nullptr, 0};
-        if ((r = exact_prepare(h, c, every, plan, h->range_expect))) return r;
+        RowSet rset{h->n, h->capn, 3, nullptr, nullptr, 0};
+        if (rows.filter >= 0) {
+            if ((r = filter_rowset(h, s, rows.filter, 3, rset))) return r;
+            if (rset.n == 0) {  // nothing allowed: no hit, no error
+                HIPCHK(h, hipMemsetAsync(o.lims, 0, (size_t)(c.B + 1) * 8, s));
+                h->have_timing = false;
+                h->have_range_stats = true;
+                h->stats_host[6] += c.B;
+                return 0;
+            }
+        }
+        if ((r = exact_prepare(h, c, rset, plan, h->range_expect))) return r;
         if (timing) HIPCHK(h, hipEventRecord(h->ev0, s));
         c.timing = timing;
         if ((r = range_exact(h, c, plan, o))) return r;
+    } else if (walk) {
+        // the filtered walk at k = ef into the handle's scratch lists, then the cut
+        c.k = std::max(ef, 1);
+        if ((r = ensure_buf(h, h->okeys, (size_t)c.B * c.k)) || (r = ensure_buf(h, h->odist, (size_t)c.B * c.k)) ||
+            (r = ensure_buf(h, h->on, (size_t)c.B)) || (r = ensure_buf(h, h->rcnt, (size_t)c.B)))
+            return r;
+        c.okeys = h->okeys.p;
+        c.odist = h->odist.p;
+        c.on = h->on.p;
+        const int32_t* fof = rows.filter_of;
+        if (c.on_device) {  // one id for the batch, filled on the stream
+            if ((r = ensure_buf(h, h->fof, (size_t)c.B))) return r;
+            HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->fof.p, rows.filter, (size_t)c.B, s));
+            fof = h->fof.p;
+        }
+        if (timing) HIPCHK(h, hipEventRecord(h->ev0, s));
+        if ((r = filtered_walk(h, c, c.k, W, fof, false))) return r;
+        LCHK(h, launch_range_beam(h->okeys.p, h->odist.p, h->on.p, c.k, o.radius, c.B, h->rcnt.p, o.lims, o.cap, o.keys,
+                                  o.dist, s));
     } else {
         c.k = std::max(ef, 1);
         const int top = top_live_layer(h);
@@ -988,38 +1099,151 @@ int range_search_device_impl(mhnsw_index* h, const float* d_queries, int64_t B, 
     return on_scratch(h, s, [&] { return range_search(h, c, mode, ef, o); });
 }
 
+// the filtered range search on device buffers: one filter for the batch (-1: the plain call)
+int range_search_filtered_device_impl(mhnsw_index* h, const float* d_queries, int64_t B, int dim, const float* d_radius,
+                                      int mode, int ef, int route, int filter, int64_t cap, int64_t* d_lims,
+                                      int64_t* d_keys, float* d_dist, hipStream_t s) {
+    if (filter == -1) return range_search_device_impl(h, d_queries, B, dim, d_radius, mode, ef, cap, d_lims, d_keys, d_dist, s);
+    SearchCall c{d_queries, true, B, dim, 1, nullptr, nullptr, nullptr, nullptr, s, true, true};
+    const RangeOut o{d_radius, cap, d_lims, d_keys, d_dist};
+    RangeRows rows;
+    rows.filter = filter;
+    rows.walk = true;
+    rows.route = route;
+    return on_scratch(h, s, [&] { return range_search(h, c, mode, ef, o, rows); });
+}
+
 // The host-pointer call: the device call into the handle's result buffers; when the hits did
 // not fit, once more with room for exactly lims[B].  The results stay there for
-// mhnsw_range_results.
+// mhnsw_range_results.  (One pass on the handle's stream, inside on_scratch.)
+static int range_host_pass(mhnsw_index* h, const float* queries, int64_t B, int dim, const float* radius, int mode,
+                           int ef, const RangeRows& rows, int64_t* out_lims) {
+    hipStream_t s = h->stream;
+    int r;
+    const int64_t nb = std::max<int64_t>(B, 0);
+    if (nb > 0 && !radius) return fail(h, MHNSW_EINVAL, "radius must be non-NULL");
+    if (!out_lims) return fail(h, MHNSW_EINVAL, "out_lims must be non-NULL");
+    if ((r = ensure_buf(h, h->rrad, (size_t)std::max<int64_t>(nb, 1))) || (r = ensure_buf(h, h->rlims, (size_t)nb + 1)))
+        return r;
+    if (nb > 0) HIPCHK(h, hipMemcpyAsync(h->rrad.p, radius, (size_t)nb * 4, hipMemcpyHostToDevice, s));
+    const int64_t room = std::max<int64_t>(0, (int64_t)0x7fffffff - h->n);
+    int64_t cap = std::min(room, std::max<int64_t>({(int64_t)h->rkeys.n, 1024, nb * h->range_expect}));
+    for (int pass = 0;; ++pass) {
+        if ((r = ensure_buf(h, h->rkeys, (size_t)std::max<int64_t>(cap, 1))) ||
+            (r = ensure_buf(h, h->rdist, (size_t)std::max<int64_t>(cap, 1))))
+            return r;
+        SearchCall c{queries, false, B, dim, 1, nullptr, nullptr, nullptr, nullptr, s, false, true};
+        const RangeOut o{h->rrad.p, cap, h->rlims.p, h->rkeys.p, h->rdist.p};
+        if ((r = range_search(h, c, mode, ef, o, rows))) return r;
+        HIPCHK(h, hipMemcpyAsync(out_lims, h->rlims.p, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost, s));
+        if ((r = read_error(h, s))) return r;
+        if (out_lims[nb] <= cap) break;
+        if (pass) return fail(h, MHNSW_EINTERNAL, "range search: %lld hits after room for %lld", (long long)out_lims[nb], (long long)cap);
+        h->stats_host[6] -= nb;  // one search, run twice
+        cap = out_lims[nb];
+    }
+    h->range_total = out_lims[nb];
+    return 0;
+}
+
 int range_search_impl(mhnsw_index* h, const float* queries, int64_t B, int dim, const float* radius, int mode, int ef,
                       int64_t* out_lims) {
-    hipStream_t s = h->stream;
     h->range_total = -1;
+    return on_scratch(h, h->stream,
+                      [&] { return range_host_pass(h, queries, B, dim, radius, mode, ef, RangeRows(), out_lims); });
+}
+
+// b grown to `need` entries, its first `used` kept (a device copy on s)
+template <class T>
+static int grow_keep(mhnsw_index* h, DevBuf<T>& b, size_t used, size_t need, hipStream_t s) {
+    if (b.n >= need) return 0;
+    DevBuf<T> nb;
+    int r = ensure_buf(h, nb, std::max(need, b.n * 2));
+    if (r) return r;
+    if (b.p && used) HIPCHK(h, hipMemcpyAsync(nb.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (b.p) (void)hipFree(b.p);
+    b = nb;
+    return 0;
+}
+
+// The filtered host call.  Beam mode is one pass for any mix of filters (the walk takes one per
+// query).  Exact mode runs one pass per distinct filter id (ascending) over that filter's
+// queries; a pass leaves its sorted hits in the staging buffers, and once every count is known
+// a device scatter (launch_range_place) moves each query's segment to its own place in the
+// result -- only the passes' lims cross to the host.  The last_range_* options then describe
+// the last pass.
+int range_search_filtered_impl(mhnsw_index* h, const float* queries, int64_t B, int dim, const float* radius, int mode,
+                               int ef, int route, const int32_t* filter_of, int64_t* out_lims) {
+    h->range_total = -1;
+    if (B > 0 && !filter_of) return fail(h, MHNSW_EINVAL, "filter_of must be non-NULL");
+    std::map<int32_t, std::vector<int64_t>> groups;
+    for (int64_t b = 0; b < B; ++b) groups[filter_of[b]].push_back(b);
+    // filter -1 for every query is the plain range search
+    if (groups.empty() || (groups.size() == 1 && groups.begin()->first == -1))
+        return range_search_impl(h, queries, B, dim, radius, mode, ef, out_lims);
+    hipStream_t s = h->stream;
+    RangeRows rows;
+    if (mode != MHNSW_MODE_EXACT || groups.size() == 1) {
+        rows.walk = true;
+        rows.route = route;
+        rows.filter_of = filter_of;
+        rows.filter = groups.size() == 1 ? groups.begin()->first : -1;
+        return on_scratch(h, s, [&] { return range_host_pass(h, queries, B, dim, radius, mode, ef, rows, out_lims); });
+    }
+    // every argument error before the first pass leaves a result
+    if (!radius) return fail(h, MHNSW_EINVAL, "radius must be non-NULL");
+    if (!out_lims) return fail(h, MHNSW_EINVAL, "out_lims must be non-NULL");
+    for (const auto& [f, qs] : groups)
+        if (f < -1 || (f >= 0 && (f >= (int)h->filters.size() || !h->filters[f].used)))
+            return fail(h, MHNSW_EINVAL, "unknown filter %d", f);
     return on_scratch(h, s, [&]() -> int {
         int r;
-        const int64_t nb = std::max<int64_t>(B, 0);
-        if (nb > 0 && !radius) return fail(h, MHNSW_EINVAL, "radius must be non-NULL");
-        if (!out_lims) return fail(h, MHNSW_EINVAL, "out_lims must be non-NULL");
-        if ((r = ensure_buf(h, h->rrad, (size_t)std::max<int64_t>(nb, 1))) || (r = ensure_buf(h, h->rlims, (size_t)nb + 1)))
-            return r;
-        if (nb > 0) HIPCHK(h, hipMemcpyAsync(h->rrad.p, radius, (size_t)nb * 4, hipMemcpyHostToDevice, s));
-        const int64_t room = std::max<int64_t>(0, (int64_t)0x7fffffff - h->n);
-        int64_t cap = std::min(room, std::max<int64_t>({(int64_t)h->rkeys.n, 1024, nb * h->range_expect}));
-        for (int pass = 0;; ++pass) {
-            if ((r = ensure_buf(h, h->rkeys, (size_t)std::max<int64_t>(cap, 1))) ||
-                (r = ensure_buf(h, h->rdist, (size_t)std::max<int64_t>(cap, 1))))
+        std::vector<float> q, rad;
+        std::vector<int64_t> glims, cnt((size_t)B), src((size_t)B);
+        int64_t staged = 0;
+        for (const auto& [f, qs] : groups) {
+            const size_t R = qs.size();
+            q.resize(R * (size_t)dim);
+            rad.resize(R);
+            glims.assign(R + 1, 0);
+            for (size_t i = 0; i < R; ++i) {
+                memcpy(&q[i * dim], queries + (size_t)qs[i] * dim, (size_t)dim * 4);
+                rad[i] = radius[qs[i]];
+            }
+            rows.filter = f;
+            if ((r = range_host_pass(h, q.data(), (int64_t)R, dim, rad.data(), mode, ef, rows, glims.data()))) {
+                h->range_total = -1;
                 return r;
-            SearchCall c{queries, false, B, dim, 1, nullptr, nullptr, nullptr, nullptr, s, false, true};
-            const RangeOut o{h->rrad.p, cap, h->rlims.p, h->rkeys.p, h->rdist.p};
-            if ((r = range_search(h, c, mode, ef, o))) return r;
-            HIPCHK(h, hipMemcpyAsync(out_lims, h->rlims.p, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost, s));
-            if ((r = read_error(h, s))) return r;
-            if (out_lims[nb] <= cap) break;
-            if (pass) return fail(h, MHNSW_EINTERNAL, "range search: %lld hits after room for %lld", (long long)out_lims[nb], (long long)cap);
-            h->stats_host[6] -= nb;  // one search, run twice
-            cap = out_lims[nb];
+            }
+            const int64_t got = glims[R];
+            h->range_total = -1;  // (the pass's hits are not the call's)
+            if ((r = grow_keep(h, h->rgkeys, (size_t)staged, (size_t)(staged + got), s)) ||
+                (r = grow_keep(h, h->rgdist, (size_t)staged, (size_t)(staged + got), s)))
+                return r;
+            if (got) {
+                HIPCHK(h, hipMemcpyAsync(h->rgkeys.p + staged, h->rkeys.p, (size_t)got * 8, hipMemcpyDeviceToDevice, s));
+                HIPCHK(h, hipMemcpyAsync(h->rgdist.p + staged, h->rdist.p, (size_t)got * 4, hipMemcpyDeviceToDevice, s));
+            }
+            for (size_t i = 0; i < R; ++i) {
+                cnt[(size_t)qs[i]] = glims[i + 1] - glims[i];
+                src[(size_t)qs[i]] = staged + glims[i];
+            }
+            staged += got;
         }
-        h->range_total = out_lims[nb];
+        out_lims[0] = 0;
+        for (int64_t b = 0; b < B; ++b) out_lims[b + 1] = out_lims[b] + cnt[(size_t)b];
+        const int64_t total = out_lims[B];
+        if (total > (int64_t)0x7fffffff) return fail(h, MHNSW_EUNSUPPORTED, "range search supports cap + rows < 2^31");
+        if ((r = ensure_buf(h, h->rlims, (size_t)B + 1)) || (r = ensure_buf(h, h->rgoff, (size_t)B)) ||
+            (r = ensure_buf(h, h->rkeys, (size_t)std::max<int64_t>(total, 1))) ||
+            (r = ensure_buf(h, h->rdist, (size_t)std::max<int64_t>(total, 1))))
+            return r;
+        HIPCHK(h, hipMemcpyAsync(h->rlims.p, out_lims, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->rgoff.p, src.data(), (size_t)B * 8, hipMemcpyHostToDevice, s));
+        LCHK(h, launch_range_place(h->rgkeys.p, h->rgdist.p, h->rgoff.p, h->rlims.p, B, h->rkeys.p, h->rdist.p, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        h->range_total = total;
         return 0;
     });
 }

@@ -16,6 +16,9 @@ MODE_EXACT   the same allow-list, searched by the engine's filtered exact
              search (brute force over the allowed rows only): the exact k
              nearest matching nodes; expandFactor, ef and route do not apply.
 
+RangeSearch (not in the reference) returns every matching node within a radius
+of the query, through the same allow-list (Graph.range_search_arrays).
+
 Go's interface{} values are Python objects here.  reflect.DeepEqual is typed:
 an int never equals a float, so values compare equal only within one type.
 """
@@ -198,7 +201,10 @@ class FacetedGraph:  # search.go:166-329
 
     def close(self):
         for _, f in self._filters.values():
-            f.close()
+            try:
+                f.close()
+            except HnswError:  # (dropped by an Import: the engine no longer knows it)
+                pass
         self._filters.clear()
 
     def Add(self, node: FacetedNode):
@@ -290,6 +296,36 @@ class FacetedGraph:  # search.go:166-329
                 f.close()
         out = []
         for key in self.Graph.decode_keys(keys[0, : n[0]]):
+            node, ok = self.Store.Get(key)
+            if ok:
+                out.append(node)
+        return out
+
+    def RangeSearch(self, query, filters, radius: float, mode: int = MODE_EXACT, ef: int = 0,
+                    route: int = 0) -> List[FacetedNode]:
+        """Every node that matches `filters` within `radius` of the query,
+        nearest first (Graph.RangeSearch over the filter list's allow-list).
+        MODE_EXACT returns all of them; MODE_BEAM the ones the filtered walk at
+        k = ef finds.  The reference has no such call: it extends Search."""
+        if mode not in (MODE_BEAM, MODE_EXACT):
+            raise FacetError(f"range search supports beam and exact mode, got mode {mode}")
+        q = np.asarray(query, np.float32).reshape(1, -1)
+        f, cached = self._device_filter(filters)
+        kw = dict(mode=mode, ef=ef, route=route)
+        try:
+            try:
+                _, keys, _ = self.Graph.range_search_arrays(q, radius, filters=f, **kw)
+            except HnswError as e:
+                if not cached or "unknown filter" not in str(e):
+                    raise
+                # the graph was Imported since: its filters are gone, the store's keys are not
+                f, cached = self._device_filter(filters, fresh=True)
+                _, keys, _ = self.Graph.range_search_arrays(q, radius, filters=f, **kw)
+        finally:
+            if not cached:
+                f.close()
+        out = []
+        for key in self.Graph.decode_keys(keys):
             node, ok = self.Store.Get(key)
             if ok:
                 out.append(node)

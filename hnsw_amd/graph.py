@@ -665,7 +665,8 @@ class Graph:
             raise HnswError(-1, f"{rad.size} radii for {len(q)} queries")
         return q, np.ascontiguousarray(np.broadcast_to(rad, (len(q),)))
 
-    def range_search_arrays(self, queries, radius, mode: int = MODE_EXACT, ef: int = 0):
+    def range_search_arrays(self, queries, radius, mode: int = MODE_EXACT, ef: int = 0, filters=None,
+                            route: int = 0):
         """Every row within `radius` of each query -> (lims int64[B + 1], keys
         int64[lims[B]], dist float32[lims[B]]): query b's hits are
         [lims[b], lims[b + 1]), ascending by (distance, row).  A hit's canonical
@@ -673,13 +674,24 @@ class Graph:
         distance for L2); a NaN or negative radius gives no hit.  radius: one
         per query, or a scalar for all.  MODE_EXACT returns every hit;
         MODE_BEAM the hits the beam search at k = ef finds (a count equal to ef
-        means the list was exhausted: raise ef or use MODE_EXACT)."""
+        means the list was exhausted: raise ef or use MODE_EXACT).
+        filters: one Filter, or one per query (None: every live row) -- only
+        allowed rows are hits.  MODE_EXACT then works over the allowed rows only
+        (one pass per distinct filter); MODE_BEAM is the filtered walk at k = ef
+        <= 128 through a list of `route` entries (0: option filter_route), cut
+        by the radius (DESIGN.md "Filtered range search")."""
         q, rad = self._range_io(queries, radius, mode)
-        self._sync()
         B, d = q.shape
+        fo = None if filters is None else np.ascontiguousarray(self._filter_ids(filters, B))
+        self._sync()
         lims = np.zeros(B + 1, np.int64)
-        self._check(load().mhnsw_range_search(self._h, _ptr(q, C.c_float), B, d, _ptr(rad, C.c_float), int(mode),
-                                              int(ef), _ptr(lims, C.c_int64)))
+        if fo is None:
+            self._check(load().mhnsw_range_search(self._h, _ptr(q, C.c_float), B, d, _ptr(rad, C.c_float), int(mode),
+                                                  int(ef), _ptr(lims, C.c_int64)))
+        else:
+            self._check(load().mhnsw_range_search_filtered(self._h, _ptr(q, C.c_float), B, d, _ptr(rad, C.c_float),
+                                                           int(mode), int(ef), int(route), _ptr(fo, C.c_int32),
+                                                           _ptr(lims, C.c_int64)))
         total = int(lims[B])
         keys, dist = np.zeros(total, np.int64), np.zeros(total, np.float32)
         self._check(load().mhnsw_range_results(self._h, _ptr(keys, C.c_int64), _ptr(dist, C.c_float), total))
@@ -695,9 +707,21 @@ class Graph:
                                                      int(mode), int(ef), int(cap), C.c_void_p(lims_ptr),
                                                      C.c_void_p(keys_ptr), C.c_void_p(dist_ptr), C.c_void_p(stream)))
 
-    def RangeSearch(self, near, radius: float, mode: int = MODE_EXACT, ef: int = 0) -> List[Node]:
+    def range_search_filtered_device(self, q_ptr: int, B: int, dim: int, radius_ptr: int, filter, cap: int,
+                                     lims_ptr: int, keys_ptr: int, dist_ptr: int, mode: int = MODE_EXACT, ef: int = 0,
+                                     route: int = 0, stream: int = 0):
+        """range_search_device among the rows of one Filter (None: every live
+        row) for the whole batch, enqueued on `stream` (no host sync); the same
+        cap / lims contract."""
+        fid = int(self._filter_ids(filter, 1)[0])
+        self._check(load().mhnsw_range_search_filtered_device(
+            self._h, C.c_void_p(q_ptr), B, dim, C.c_void_p(radius_ptr), int(mode), int(ef), int(route), fid, int(cap),
+            C.c_void_p(lims_ptr), C.c_void_p(keys_ptr), C.c_void_p(dist_ptr), C.c_void_p(stream)))
+
+    def RangeSearch(self, near, radius: float, mode: int = MODE_EXACT, ef: int = 0, filter=None,
+                    route: int = 0) -> List[Node]:
         q = np.asarray(near, np.float32).reshape(1, -1)
-        _, keys, _ = self.range_search_arrays(q, radius, mode=mode, ef=ef)
+        _, keys, _ = self.range_search_arrays(q, radius, mode=mode, ef=ef, filters=filter, route=route)
         return self._nodes(keys)
 
     def _node(self, key) -> Node:

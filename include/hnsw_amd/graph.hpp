@@ -414,14 +414,33 @@ class Graph {  // graph.go:305-332
     };
     std::pair<std::vector<RangeHit>, Error> RangeSearch(const Vector& near, float radius, int mode = MHNSW_MODE_EXACT,
                                                         int ef = 0) {
+        return range_search(near, radius, nullptr, false, mode, ef, 0);
+    }
+    // ... among the rows of `filter` only (mhnsw.h "filtered range search"; nullptr: every live
+    // row, the call above).  MHNSW_MODE_EXACT works over the allowed rows alone;
+    // MHNSW_MODE_BEAM is the filtered walk at k = ef <= 128 through a list of `route` entries
+    // (<= 0: the option filter_route), cut by the radius.
+    std::pair<std::vector<RangeHit>, Error> RangeSearch(const Vector& near, float radius, const Filter* filter,
+                                                        int mode = MHNSW_MODE_EXACT, int ef = 0, int route = 0) {
+        return range_search(near, radius, filter, true, mode, ef, route);
+    }
+
+   private:
+    std::pair<std::vector<RangeHit>, Error> range_search(const Vector& near, float radius, const Filter* filter,
+                                                         bool filtered, int mode, int ef, int route) {
         sync();
         const int have = Dims();
         if (have && (int)near.size() != have)
             return {{}, Error{"embedding dimension mismatch: " + std::to_string(have) + " != " +
                                   std::to_string(near.size()),
                               MHNSW_EDIM}};
+        if (filter && filter->Owner() != this) return {{}, Error{"filter of another graph", MHNSW_EINVAL}};
+        if (filter && filter->Id() < 0) return {{}, Error{"unknown filter -1", MHNSW_EINVAL}};  // closed, or never made
+        const int32_t fo = filter ? filter->Id() : -1;
         int64_t lims[2] = {0, 0};
-        int rc = mhnsw_range_search(h_, near.data(), 1, (int)near.size(), &radius, mode, ef, lims);
+        int rc = filtered ? mhnsw_range_search_filtered(h_, near.data(), 1, (int)near.size(), &radius, mode, ef, route,
+                                                        &fo, lims)
+                          : mhnsw_range_search(h_, near.data(), 1, (int)near.size(), &radius, mode, ef, lims);
         if (rc < 0) return {{}, make_error(rc, h_)};
         std::vector<int64_t> keys((size_t)lims[1]);
         std::vector<float> dist((size_t)lims[1]);
@@ -433,7 +452,6 @@ class Graph {  // graph.go:305-332
         return {out, {}};
     }
 
-   private:
     std::pair<std::vector<Node<K>>, Error> search_filtered(const Vector& near, int k, const Filter* filter, int ef,
                                                            int route, bool exact) {
         sync();

@@ -348,6 +348,46 @@ int mhnsw_range_search(mhnsw_index *h, const float *queries, int64_t B, int dim,
 int mhnsw_range_results(mhnsw_index *h, int64_t *out_keys, float *out_dist, int64_t cap);
 int mhnsw_range_search_device(mhnsw_index *h, const float *d_queries, int64_t B, int dim, const float *d_radius, int mode,
                               int ef, int64_t cap, int64_t *d_lims, int64_t *d_keys, float *d_dist, void *stream);
+/* The filtered range search: every allowed row within a radius (the reference's
+ * facets/search.go searches a facet's rows by k; this extends that interface
+ * by a radius; DESIGN.md "Filtered range search").  For query b with radius
+ * radius[b] and filter f_b a row is a hit iff its bit is set in f_b, a
+ * MHNSW_MODE_EXACT search could return it (not deleted, not left partial by a
+ * failed insert), and its canonical float32 distance d is finite with
+ * d <= radius[b] (the square-rooted distance for MHNSW_EUCLIDEAN).  The result
+ * has mhnsw_range_search's ragged shape and order; a NaN or negative radius
+ * gives what it gives there, an empty allow-set zero hits and no error, and
+ * filter -1 is mhnsw_range_search itself (the same code path, the same bytes).
+ * MHNSW_MODE_EXACT is the range search over the filter's rows as a gathered row
+ * set (the filtered exact search's): the filter GEMM, the canonical check and
+ * the sweep all run over the m allowed rows, so a call costs what m rows cost,
+ * not what the index costs; with fewer than 256 allowed rows the sweep over the
+ * id list is the whole path.  Every build mode works, MHNSW_BUILD_FLAT included.
+ * MHNSW_MODE_BEAM returns the hits the filtered walk finds: mhnsw_search_filtered
+ * at k = ef through a route list of `route` entries (0: option filter_route),
+ * cut by the radius, with that call's limits and messages ("filtered search
+ * supports max(ef,k) <= 128", "filtered search supports route <= 2048"); a
+ * count equal to ef means the list was exhausted.  route is ignored in exact mode.
+ * mhnsw_range_search_filtered: filter_of[b] (host) is query b's filter, -1 for
+ * every live row.  Synchronous; the hits are left for mhnsw_range_results, with
+ * the second run when they do not fit.  Exact mode groups the batch by filter
+ * and runs one pass per distinct id; the passes' ragged results are moved on
+ * the device to each query's own segment (only the passes' lims cross to the
+ * host), and the last_* options then describe the last pass.  Beam mode is one
+ * launch for any mix.
+ * mhnsw_range_search_filtered_device: one filter (or -1) for the whole batch,
+ * enqueued on `stream` without a host synchronisation, with the cap / true-lims
+ * contract of mhnsw_range_search_device; exact mode needs cap + m < 2^31 (m:
+ * the allowed rows).  A caller with a mixed batch groups it.
+ * Errors: MHNSW_EINVAL "unknown filter %d"; MHNSW_EUNSUPPORTED "range search
+ * supports beam and exact mode".  The last_range_* options apply as they are; a
+ * filtered exact pass also fills last_fx_compact_ns and last_fx_gather_ns (its
+ * row set's id list and plane).  Measurements: profiles/filtered_range.txt. */
+int mhnsw_range_search_filtered(mhnsw_index *h, const float *queries, int64_t B, int dim, const float *radius,
+                                int mode, int ef, int route, const int32_t *filter_of, int64_t *out_lims);
+int mhnsw_range_search_filtered_device(mhnsw_index *h, const float *d_queries, int64_t B, int dim,
+                                       const float *d_radius, int mode, int ef, int route, int filter, int64_t cap,
+                                       int64_t *d_lims, int64_t *d_keys, float *d_dist, void *stream);
 
 /* ---- SearchWithNegative(s) / BatchSearchWithNegatives (graph.go:1116-1537) ----
  * Query b's negatives are the next neg_count[b] rows of `negatives` (B*dim
