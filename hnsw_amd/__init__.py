@@ -7,7 +7,8 @@ Go API (Graph, Node, CosineDistance, ...).  There is no CPU fallback.
 """
 from ._lib import (BUILD_BATCH, BUILD_COMPAT, BUILD_FLAT, COSINE, EUCLIDEAN, KEY_INT, KEY_INT32, KEY_INT64, KEY_STRING, KEY_UINT32,
                    KEY_UINT64, MODE_BEAM, MODE_COMPAT, MODE_EXACT, HnswError, LIB_PATH, SIGNATURES, load)
-from .graph import (DOG_QUERY_HACK, CosineDistance, DistanceFunc, EuclideanDistance, Filter, Graph, LoadSavedGraph, MakeNode,
+from .graph import (DOG_QUERY_HACK, Analyzer, CosineDistance, DistanceFunc, EuclideanDistance, Filter, Graph, GraphQualityMetrics, GraphReachability,
+                    LoadSavedGraph, MakeNode,
                     NewGraph, NewGraphWithConfig, Node, RegisterDistanceFunc, SavedGraph, SplitMix64Rand, Vector,
                     distance_func_to_name, max_level, merge_topk_device, random_level, split_ragged, sweep_device)
 from .adapters import ExactAdapter, ExactIndex, HNSWAdapter
@@ -18,5 +19,5 @@ __all__ = [
     "NewGraph", "NewGraphWithConfig", "Node", "RegisterDistanceFunc", "Vector", "distance_func_to_name",
     "merge_topk_device", "KEY_INT", "KEY_INT32", "KEY_INT64", "KEY_UINT32", "KEY_UINT64", "LoadSavedGraph",
     "SavedGraph", "sweep_device", "DOG_QUERY_HACK", "SplitMix64Rand", "max_level", "random_level",
-    "split_ragged",
+    "split_ragged", "Analyzer", "GraphQualityMetrics", "GraphReachability",
 ]

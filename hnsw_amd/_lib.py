@@ -78,6 +78,12 @@ SIGNATURES = {
     "mhnsw_update": (C.c_int, [_vp, _i64p, _f32p, C.c_int64, C.c_int, _u8p]),
     "mhnsw_update_device": (C.c_int, [_vp, _i64p, _vp, C.c_int64, C.c_int, _u8p]),
     "mhnsw_export_edge_dist": (C.c_int, [_vp, _f32p, C.c_int]),
+    "mhnsw_relink": (C.c_int, [_vp, _i64p, C.c_int64, _u8p]),
+    "mhnsw_quality_metrics": (C.c_int, [_vp, _vp]),
+    "mhnsw_degree_histogram": (C.c_int, [_vp, C.c_int, _i64p]),
+    "mhnsw_hops": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, _i32p]),
+    "mhnsw_reachability": (C.c_int, [_vp, _i64p, _i64p, _i32p, C.c_int, _i64p]),
+    "mhnsw_unreachable_keys": (C.c_int, [_vp, _i64p, C.c_int64]),
     "mhnsw_distance": (C.c_int, [C.c_int, _f32p, _f32p, C.c_int64, C.c_int, _f32p]),
     "mhnsw_distance_device": (C.c_int, [C.c_int, _vp, _vp, C.c_int64, C.c_int, _vp, _vp]),
     "mhnsw_export_sizes": (C.c_int, [_vp, _i64p, _P(C.c_int), _P(C.c_int), _P(C.c_int)]),

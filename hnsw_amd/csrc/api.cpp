@@ -1293,6 +1293,20 @@ void mhnsw_destroy(mhnsw_index* h) {
     F(h->rgoff.p);
     F(h->uids.p);
     F(h->d_repaired);
+    F(h->an_bits.p);
+    F(h->an_q.p);
+    F(h->an_ids.p);
+    F(h->an_blk.p);
+    F(h->an_hm.p);
+    F(h->an_mask.p);
+    F(h->an_sidx.p);
+    F(h->an_hops.p);
+    F(h->an_cnt.p);
+    F(h->an_keys.p);
+    F(h->an_rows.p);
+    F(h->an_dist.p);
+    if (h->aev0) (void)hipEventDestroy(h->aev0);
+    if (h->aev1) (void)hipEventDestroy(h->aev1);
     for (auto e : h->uev) (void)hipEventDestroy(e);
     for (auto e : h->fxev)
         if (e) (void)hipEventDestroy(e);
@@ -1587,6 +1601,17 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
     else if (n == "last_update_detach_ns") *v = (int64_t)std::llround(h->update_us[0] * 1e3);
     else if (n == "last_update_overwrite_ns") *v = (int64_t)std::llround(h->update_us[1] * 1e3);
     else if (n == "last_update_insert_ns") *v = (int64_t)std::llround(h->update_us[2] * 1e3);
+    // read-only, analyzer: device time of the last mhnsw_reachability (HIP events), and the bytes its
+    // scratch buffers hold
+    else if (n == "last_reach_ns") {
+        float ms = 0.f;
+        if (!h->have_reach_timing || hipEventElapsedTime(&ms, h->aev0, h->aev1) != hipSuccess) return MHNSW_EINVAL;
+        *v = (int64_t)std::llround((double)ms * 1e6);
+    }
+    else if (n == "last_analyzer_scratch_bytes")
+        *v = (int64_t)(4 * (h->an_bits.n + h->an_q.n + h->an_ids.n + h->an_blk.n + h->an_hm.n + h->an_sidx.n +
+                            h->an_hops.n + h->an_rows.n + h->an_dist.n) +
+                       h->an_mask.n + 8 * (h->an_cnt.n + h->an_keys.n));
     else if (n == "range_expect") *v = h->range_expect;
     else if (n == "range_force_fallback") *v = h->range_force_fallback;
     else if (n == "last_range_candidates" || n == "last_range_fallback_queries") {
@@ -2051,14 +2076,17 @@ int mhnsw_replace(mhnsw_index* h, const int64_t* keys, const float* vecs, int64_
 // Update: new vectors for present keys, in place (include/mhnsw.h; the device steps: update.hip).
 // Rows keep their ids, levels, layer membership and filter bits; the host mirrors (key map,
 // hdead, hmask, layer counts and entries) and the Rng are not written at all.
+// Relink (mhnsw_relink) is the same call with each found row's stored vector: `relink` skips the
+// staging and the overwrite step, which would write back what the store already holds.
 static int update_impl(mhnsw_index* h, const int64_t* keys, const float* vecs, bool on_device, int64_t n, int dim,
-                       uint8_t* out_found) {
-    if (n > 0 && (!keys || !vecs || !out_found))
+                       uint8_t* out_found, bool relink = false) {
+    if (relink && n > 0 && (!keys || !out_found)) return fail(h, MHNSW_EINVAL, "keys and out_found must be non-NULL");
+    if (!relink && n > 0 && (!keys || !vecs || !out_found))
         return fail(h, MHNSW_EINVAL, "keys, vecs and out_found must be non-NULL");
     if (h->build_mode == MHNSW_BUILD_COMPAT || h->aliased || h->partial_rows > 0)
         return fail(h, MHNSW_EUNSUPPORTED, "update needs a batch or flat (build_mode 1 or 2) handle");
     if (n <= 0) return MHNSW_OK;
-    if (h->layers_exist && dim != h->dim)
+    if (!relink && h->layers_exist && dim != h->dim)
         return fail(h, MHNSW_EDIM, "embedding dimension mismatch: %d != %d", h->dim, dim);
     {
         std::unordered_set<int64_t> seen;
@@ -2088,18 +2116,19 @@ static int update_impl(mhnsw_index* h, const int64_t* keys, const float* vecs, b
     if (!flat && (r = ensure_batch_scratch(h))) return r;
     // staging: the call's vectors (a host call's go through tmp), all n padded, the id lists
     const size_t raw = on_device ? 0 : ((size_t)n * dim + 3) / 4 * 4;  // (the padded rows stay 16-byte aligned)
-    if ((r = ensure_buf(h, h->tmp, raw + (size_t)n * h->pitch)) || (r = ensure_buf(h, h->uids, 2 * (size_t)m))) return r;
+    if ((!relink && (r = ensure_buf(h, h->tmp, raw + (size_t)n * h->pitch))) || (r = ensure_buf(h, h->uids, 2 * (size_t)m)))
+        return r;
     if (!h->d_repaired && hipMalloc(&h->d_repaired, sizeof(unsigned long long)) != hipSuccess)
         return fail(h, MHNSW_ENOMEM, "device allocation failed");
     const float* src = vecs;
-    if (!on_device) {
+    if (!on_device && !relink) {
         HIPCHK(h, hipMemcpyAsync(h->tmp.p, vecs, (size_t)n * dim * 4, hipMemcpyHostToDevice, s));
         src = h->tmp.p;
     }
-    float* padded = h->tmp.p + raw;
+    float* padded = relink ? nullptr : h->tmp.p + raw;
     uint32_t* d_ids = h->uids.p;
     uint32_t* d_from = h->uids.p + m;
-    LCHK(h, launch_pad_rows(src, n, dim, padded, h->pitch, s));
+    if (!relink) LCHK(h, launch_pad_rows(src, n, dim, padded, h->pitch, s));
     HIPCHK(h, hipMemcpyAsync(d_ids, ids.data(), (size_t)m * 4, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(d_from, from.data(), (size_t)m * 4, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemsetAsync(h->d_repaired, 0, sizeof(unsigned long long), s));
@@ -2151,25 +2180,27 @@ static int update_impl(mhnsw_index* h, const int64_t* keys, const float* vecs, b
         }
         if ((r = mark())) return r;
         // overwrite: vectors, norms, the screening copy and the exact path's planes, by row list
-        LCHK(h, launch_update_scatter(padded, d_ids + c0, d_from + c0, cnt, h->pitch, h->vecs, s));
-        LCHK(h, launch_norms_ids(h->vecs, d_ids + c0, cnt, h->pitch, h->lpr, h->vpl, h->norms, s));
-        if (h->screen & 1 && h->h16 && h->h16_metric == h->metric)
-            LCHK(h, launch_h16_rows_ids(h->vecs, h->norms, d_ids + c0, cnt, h->pitch, h->metric, h->h16, h->h16aux,
-                                        h->h16err, s));
-        // (planes converted so far, in a buffer of the current capacity: rows past xsplit_rows are
-        // written to the values the next exact search gives them anyway; an unconverted or
-        // outgrown buffer is rebuilt by that search)
-        if (h->xsplit_rows > 0 && h->xsplit.p && h->xsplit_plane == h->capn * h->pitch &&
-            h->xsplit.n >= (size_t)h->xsplit_plane * 2) {
-            uint16_t* xh = h->xsplit.p;
-            if (h->xsplit_kind == 2 && h->xinv.n >= (size_t)h->capn && h->xerr.p)
-                LCHK(h, launch_split_h16_ids(h->vecs, d_ids + c0, cnt, h->pitch, h->capn, xh, nullptr, h->xinv.p,
-                                             h->xerr.p, s));
-            else if (h->xsplit_kind == 1)
-                LCHK(h, launch_split_rows_ids(h->vecs, d_ids + c0, cnt, h->pitch, h->capn, xh,
-                                              xh + (size_t)h->capn * h->pitch, s));
-            else
-                h->xsplit_rows = 0;
+        if (!relink) {
+            LCHK(h, launch_update_scatter(padded, d_ids + c0, d_from + c0, cnt, h->pitch, h->vecs, s));
+            LCHK(h, launch_norms_ids(h->vecs, d_ids + c0, cnt, h->pitch, h->lpr, h->vpl, h->norms, s));
+            if (h->screen & 1 && h->h16 && h->h16_metric == h->metric)
+                LCHK(h, launch_h16_rows_ids(h->vecs, h->norms, d_ids + c0, cnt, h->pitch, h->metric, h->h16,
+                                            h->h16aux, h->h16err, s));
+            // (planes converted so far, in a buffer of the current capacity: rows past xsplit_rows are
+            // written to the values the next exact search gives them anyway; an unconverted or
+            // outgrown buffer is rebuilt by that search)
+            if (h->xsplit_rows > 0 && h->xsplit.p && h->xsplit_plane == h->capn * h->pitch &&
+                h->xsplit.n >= (size_t)h->xsplit_plane * 2) {
+                uint16_t* xh = h->xsplit.p;
+                if (h->xsplit_kind == 2 && h->xinv.n >= (size_t)h->capn && h->xerr.p)
+                    LCHK(h, launch_split_h16_ids(h->vecs, d_ids + c0, cnt, h->pitch, h->capn, xh, nullptr, h->xinv.p,
+                                                 h->xerr.p, s));
+                else if (h->xsplit_kind == 1)
+                    LCHK(h, launch_split_rows_ids(h->vecs, d_ids + c0, cnt, h->pitch, h->capn, xh,
+                                                  xh + (size_t)h->capn * h->pitch, s));
+                else
+                    h->xsplit_rows = 0;
+            }
         }
         if ((r = mark())) return r;
         if (!flat) {
@@ -2228,6 +2259,12 @@ int mhnsw_update_device(mhnsw_index* h, const int64_t* keys, const float* d_vecs
     HIPCHK(h, hipDeviceSynchronize());  // order after whatever produced d_vecs (and any enqueued search)
     h->scr_valid = false;
     return update_impl(h, keys, d_vecs, true, n, dim, out_found);
+}
+
+int mhnsw_relink(mhnsw_index* h, const int64_t* keys, int64_t n, uint8_t* out_found) {
+    std::unique_lock<std::shared_mutex> lk(h->mu);
+    if (int r0 = drain(h)) return r0;
+    return update_impl(h, keys, nullptr, false, n, h->dim, out_found, true);
 }
 
 int mhnsw_export_edge_dist(mhnsw_index* h, float* adjd, int cap) {

@@ -387,6 +387,33 @@ int launch_update_detach(int32_t* deg, int32_t* adj, float* adjd, int cap, int64
 int launch_update_scatter(const float* src, const uint32_t* ids, const uint32_t* from, int64_t m, int pitch, float* dst,
                           hipStream_t s);
 
+// ---- analyzer: degree histogram, reachability, hop matrix (analyze.hip) ----
+constexpr int AN_BINS = 256;      // degree bins on the device (a row cap past it is refused by the host)
+constexpr int AN_MAX_KEYS = 128;  // sources of one hop BFS: one bit each of a row's 128-bit masks
+// hist[d] += live members (deg != -2, dead byte clear; dead nullable) of degree d among rows [0, n)
+int launch_an_degree(const int32_t* deg, const uint8_t* dead, int64_t n, unsigned long long* hist, hipStream_t s);
+// The reachability bitmaps cover `rows` rows, a multiple of 64 at or past the row capacity; the
+// queues hold `rows` entries.  seed: vis &= members of the layer (deg != -2), the rows left are
+// queued (*qcnt += their number).  level: one BFS level from cur[0 .. ncur) -- rows visited
+// first set their bit and join `next` (*ncnt += their number, any order); ids at or past capn
+// set err bit 4 and are skipped.  count: cnt[0] += live members, cnt[1] += the visited ones,
+// unr (nullable) = the live members not visited.
+int launch_an_seed(const int32_t* deg, int64_t n, int64_t rows, uint32_t* vis, uint32_t* q, uint32_t* qcnt,
+                   hipStream_t s);
+int launch_an_level(const int32_t* deg, const int32_t* adj, int cap, uint32_t capn, const uint32_t* cur, uint32_t ncur,
+                    uint32_t* vis, uint32_t* next, uint32_t* ncnt, int* err, hipStream_t s);
+int launch_an_count(const int32_t* deg, const uint8_t* dead, int64_t n, int64_t rows, const uint32_t* vis, uint32_t* unr,
+                    unsigned long long* cnt, hipStream_t s);
+int launch_an_keys(const int64_t* keys, const uint32_t* ids, int64_t m, int64_t* out, hipStream_t s);  // out[i] = keys[ids[i]]
+// Hop BFS from the ns <= AN_MAX_KEYS distinct rows src: seen / cur / next [4 * rows] words (zeroed),
+// sidx [rows] (-1).  push + settle are one level; settle writes hops[i * ns + j] = level for
+// source i reaching source row j now, and *any |= 1 while a frontier is left.
+int launch_an_hops_init(const uint32_t* src, int ns, uint32_t* seen, uint32_t* cur, int32_t* sidx, hipStream_t s);
+int launch_an_hops_push(const int32_t* deg, const int32_t* adj, int cap, uint32_t capn, int64_t n, const uint32_t* seen,
+                        const uint32_t* cur, uint32_t* next, int* err, hipStream_t s);
+int launch_an_hops_settle(int64_t rows, uint32_t* seen, uint32_t* cur, uint32_t* next, const int32_t* sidx, int ns,
+                          int level, int32_t* hops, uint32_t* any, hipStream_t s);
+
 // certificate of the re-rank (nullable pieces disable it)
 struct CertArgs {
     const float* bound;          // [B] from k_select; nullptr = no certificate

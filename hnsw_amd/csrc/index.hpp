@@ -284,6 +284,20 @@ struct mhnsw_index {
     DevBuf<uint32_t> uids;
     unsigned long long* d_repaired = nullptr;
     std::vector<hipEvent_t> uev;
+    // analyzer (analyze_host.cpp), grow-only: the reachability BFS's bitmaps (visited, unreachable),
+    // its two queues, the compaction's workspace and id list, the counters; the hop BFS's masks,
+    // source index and matrix; the sample rows and their distances.  The calls hold `mu` shared
+    // and an_mu for this state; of the last reachability the events and the unreachable keys.
+    DevBuf<uint32_t> an_bits, an_q, an_ids, an_blk, an_hm;
+    DevBuf<uint8_t> an_mask;
+    DevBuf<int32_t> an_sidx, an_hops;
+    DevBuf<unsigned long long> an_cnt;
+    DevBuf<int64_t> an_keys;
+    DevBuf<float> an_rows, an_dist;
+    hipEvent_t aev0 = nullptr, aev1 = nullptr;
+    bool have_reach_timing = false;
+    std::vector<int64_t> an_unreach;
+    std::mutex an_mu;
     std::string err;
     mutable std::shared_mutex mu;
 };

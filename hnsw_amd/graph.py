@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from dataclasses import dataclass, field
 from typing import Iterable, List, NamedTuple, Optional, Sequence
 
 import numpy as np
@@ -544,6 +545,34 @@ class Graph:
             self.BatchAdd(fresh)
         return found
 
+    def Relink(self, keys) -> List[bool]:
+        """Rebuild the graph around present keys from their stored vectors (mhnsw_relink):
+        what Update with each key's own vector does, without sending or rewriting a vector.
+        -> which keys were present.  The remedy for Analyzer.Reachability()'s unreachable keys."""
+        keys = list(keys)
+        if not keys:
+            return []
+        self._sync()
+        imgs = np.ascontiguousarray(self.encode_keys(keys), np.int64)
+        known = np.ones(len(imgs), bool)
+        if self._kt == "str":
+            if len(set(keys)) != len(keys):
+                dup = next(k for i, k in enumerate(keys) if k in keys[:i])
+                raise HnswError(-1, f"duplicate key {dup!r} in update")
+            known = imgs != np.iinfo(np.int64).min
+        out = np.zeros(len(imgs), bool)
+        if known.any():
+            out[known] = self.relink_arrays(imgs[known])
+        return [bool(x) for x in out]
+
+    def relink_arrays(self, keys) -> np.ndarray:
+        """Array form of Relink: keys int64[n] (engine images)."""
+        self._sync()
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        out = np.zeros(max(len(keys), 1), np.uint8)
+        self._check(load().mhnsw_relink(self._h, _ptr(keys, C.c_int64), len(keys), _ptr(out, C.c_uint8)))
+        return out[: len(keys)].astype(bool)
+
     def contains(self, keys) -> np.ndarray:
         """Which keys have a live node (engine key images for a list of Go keys)."""
         imgs = np.ascontiguousarray(self.encode_keys(list(keys)), np.int64)
@@ -1005,6 +1034,94 @@ class Graph:
         self._check(load().mhnsw_import(self._h, N, vecs.shape[1], L, adj.shape[2], _ptr(keys, C.c_int64),
                                         _ptr(vecs, C.c_float), _ptr(deg, C.c_int32), _ptr(adj, C.c_int32),
                                         _ptr(entry, C.c_int32), None if dd is None else _ptr(dd, C.c_uint8)))
+
+
+@dataclass
+class GraphQualityMetrics:
+    """analyzer.go:69-90."""
+    NodeCount: int = 0
+    AvgConnectivity: float = 0.0
+    ConnectivityStdDev: float = 0.0
+    DistortionRatio: float = 0.0
+    LayerBalance: float = 0.0
+    GraphHeight: int = 0
+
+
+@dataclass
+class GraphReachability:
+    """Analyzer.Reachability(): per layer the live members, those a search can reach from the
+    top layer's entry, and the BFS levels run; the keys of the unreachable live layer-0 rows
+    in ascending row id."""
+    members: List[int] = field(default_factory=list)
+    reached: List[int] = field(default_factory=list)
+    depth: List[int] = field(default_factory=list)
+    unreachable_keys: list = field(default_factory=list)
+
+
+class _Quality(C.Structure):  # include/mhnsw.h mhnsw_quality
+    _fields_ = [("node_count", C.c_int64), ("avg_connectivity", C.c_double), ("connectivity_std_dev", C.c_double),
+                ("distortion_ratio", C.c_double), ("layer_balance", C.c_double), ("graph_height", C.c_int64)]
+
+
+class Analyzer:
+    """analyzer.go:12-14 Analyzer[K]{Graph}: the graph inspected on the device (no vector or
+    adjacency row leaves it), plus Hops, DegreeHistogram, Reachability and Repair."""
+
+    def __init__(self, Graph: Graph):
+        self.Graph = Graph
+
+    def Height(self) -> int:  # analyzer.go:16-18
+        return int(load().mhnsw_num_layers(self.Graph._h))
+
+    def Topography(self) -> List[int]:  # analyzer.go:41-47
+        return self.Graph.Topography()
+
+    def Connectivity(self) -> List[float]:  # analyzer.go:22-38
+        return self.Graph.Connectivity()
+
+    def QualityMetrics(self) -> GraphQualityMetrics:  # analyzer.go:51-67
+        g = self.Graph
+        g._sync()
+        q = _Quality()
+        g._check(load().mhnsw_quality_metrics(g._h, C.byref(q)))
+        return GraphQualityMetrics(int(q.node_count), q.avg_connectivity, q.connectivity_std_dev, q.distortion_ratio,
+                                   q.layer_balance, int(q.graph_height))
+
+    def DegreeHistogram(self, layer: int = 0) -> np.ndarray:
+        """int64[64]: live members of `layer` by degree."""
+        out = np.zeros(64, np.int64)
+        self.Graph._check(load().mhnsw_degree_histogram(self.Graph._h, int(layer), _ptr(out, C.c_int64)))
+        return out
+
+    def Hops(self, keys, max_depth: int = 10) -> np.ndarray:
+        """int32[n, n]: edges on the shortest directed layer-0 path keys[i] -> keys[j]
+        (analyzer.go:193-240 for every pair), -1 beyond max_depth."""
+        g = self.Graph
+        keys = list(keys)
+        imgs = np.ascontiguousarray(g.encode_keys(keys), np.int64)
+        out = np.zeros((max(len(imgs), 1), max(len(imgs), 1)), np.int32)
+        g._check(load().mhnsw_hops(g._h, _ptr(imgs, C.c_int64), len(imgs), int(max_depth), _ptr(out, C.c_int32)))
+        return out[: len(imgs), : len(imgs)]
+
+    def Reachability(self) -> GraphReachability:
+        g = self.Graph
+        members, reached = np.zeros(32, np.int64), np.zeros(32, np.int64)
+        depth = np.zeros(32, np.int32)
+        m = C.c_int64()
+        L = g._check(load().mhnsw_reachability(g._h, _ptr(members, C.c_int64), _ptr(reached, C.c_int64),
+                                               _ptr(depth, C.c_int32), 32, C.byref(m)))
+        imgs = np.zeros(max(m.value, 1), np.int64)
+        g._check(load().mhnsw_unreachable_keys(g._h, _ptr(imgs, C.c_int64), m.value))
+        return GraphReachability(members[:L].tolist(), reached[:L].tolist(), depth[:L].tolist(),
+                                 g.decode_keys(imgs[: m.value]))
+
+    def Repair(self):
+        """Relink the unreachable layer-0 keys once -> (unreachable before, unreachable after).
+        The second number is whatever the relinked graph gives: not necessarily 0."""
+        before = self.Reachability().unreachable_keys
+        if before:
+            self.Graph.Relink(before)
+        return len(before), len(self.Reachability().unreachable_keys) if before else 0
 
 
 class SavedGraph(Graph):

@@ -621,6 +621,42 @@ class Graph {  // graph.go:305-332
         return u;
     }
 
+    // Relink (mhnsw.h "Relink"): the graph around present keys rebuilt from their stored vectors --
+    // Update with each key's own vector, no vector sent or rewritten.  first[i]: keys[i] was present.
+    std::pair<std::vector<bool>, Error> Relink(const std::vector<K>& keys) {
+        std::vector<bool> found(keys.size(), false);
+        if (keys.empty()) return {found, {}};
+        sync();
+        const std::vector<int64_t> img = Codec::encode(h_, keys, false);
+        const bool labels = Codec::kind == MHNSW_KEY_STRING;
+        std::vector<size_t> at;
+        std::vector<int64_t> ks;
+        for (size_t i = 0; i < keys.size(); ++i) {
+            if (labels) {  // (as in Update: unknown strings are absent, repeated ones checked here)
+                for (size_t j = 0; j < i; ++j)
+                    if (keys[j] == keys[i]) {
+                        Error e;
+                        e.code = MHNSW_EINVAL;
+                        e.msg = "duplicate key in update";
+                        return {found, e};
+                    }
+                if (img[i] == std::numeric_limits<int64_t>::min()) continue;
+            }
+            at.push_back(i);
+            ks.push_back(img[i]);
+        }
+        if (at.empty()) return {found, {}};
+        std::vector<uint8_t> out(at.size(), 0);
+        const int rc = mhnsw_relink(h_, ks.data(), (int64_t)ks.size(), out.data());
+        if (rc < 0) return {found, make_error(rc, h_)};
+        for (size_t j = 0; j < at.size(); ++j) found[at[j]] = out[j] != 0;
+        return {found, {}};
+    }
+
+    // (the key codec, for Analyzer<K>)
+    std::vector<int64_t> EncodeKeys(const std::vector<K>& keys) { return Codec::encode(h_, keys, false); }
+    std::vector<K> DecodeKeys(const std::vector<int64_t>& images) { return Codec::decode(h_, images.data(), images.size()); }
+
    private:
     // nodes[0, n) of dimension d through mhnsw_add, levels drawn as the walk goes
     Error addWalk(const std::vector<Node<K>>& nodes, size_t n, size_t d, const std::vector<int32_t>* levels) {
@@ -696,6 +732,95 @@ class Graph {  // graph.go:305-332
 
     mhnsw_index* h_ = nullptr;
     std::map<K, Vector> values_;
+};
+
+// analyzer.go:69-90
+struct GraphQualityMetrics {
+    int NodeCount = 0;
+    double AvgConnectivity = 0, ConnectivityStdDev = 0, DistortionRatio = 0, LayerBalance = 0;
+    int GraphHeight = 0;
+};
+
+// Analyzer.Reachability: per layer the live members, those a search can reach from the top
+// layer's entry and the BFS levels run; the keys of the unreachable live layer-0 rows
+template <class K>
+struct GraphReachability {
+    std::vector<int64_t> members, reached;
+    std::vector<int> depth;
+    std::vector<K> unreachable_keys;
+};
+
+// analyzer.go:12-14 Analyzer[K]{Graph}, on the device (mhnsw.h "Analyzer")
+template <class K>
+struct Analyzer {
+    hnsw::Graph<K>* Graph = nullptr;
+
+    int Height() const { return mhnsw_num_layers(Graph->handle()); }       // analyzer.go:16-18
+    std::vector<int> Topography() const { return Graph->Topography(); }    // analyzer.go:41-47
+    std::vector<double> Connectivity() { return Graph->Connectivity(); }   // analyzer.go:22-38
+
+    std::pair<GraphQualityMetrics, Error> QualityMetrics() {  // analyzer.go:51-67
+        mhnsw_quality q;
+        GraphQualityMetrics m;
+        const int rc = mhnsw_quality_metrics(Graph->handle(), &q);
+        if (rc < 0) return {m, make_error(rc, Graph->handle())};
+        m.NodeCount = (int)q.node_count;
+        m.AvgConnectivity = q.avg_connectivity;
+        m.ConnectivityStdDev = q.connectivity_std_dev;
+        m.DistortionRatio = q.distortion_ratio;
+        m.LayerBalance = q.layer_balance;
+        m.GraphHeight = (int)q.graph_height;
+        return {m, {}};
+    }
+
+    // live members of `layer` by degree, 64 bins
+    std::pair<std::vector<int64_t>, Error> DegreeHistogram(int layer = 0) {
+        std::vector<int64_t> h(64, 0);
+        const int rc = mhnsw_degree_histogram(Graph->handle(), layer, h.data());
+        if (rc < 0) return {{}, make_error(rc, Graph->handle())};
+        return {h, {}};
+    }
+
+    // [n * n]: edges on the shortest directed layer-0 path keys[i] -> keys[j], -1 beyond max_depth
+    std::pair<std::vector<int32_t>, Error> Hops(const std::vector<K>& keys, int max_depth = 10) {
+        const std::vector<int64_t> img = Graph->EncodeKeys(keys);
+        std::vector<int32_t> out(keys.size() * keys.size() + 1, -1);
+        const int rc = mhnsw_hops(Graph->handle(), img.data(), (int)img.size(), max_depth, out.data());
+        if (rc < 0) return {{}, make_error(rc, Graph->handle())};
+        out.resize(keys.size() * keys.size());
+        return {out, {}};
+    }
+
+    std::pair<GraphReachability<K>, Error> Reachability() {
+        GraphReachability<K> r;
+        std::vector<int64_t> mem(32), rea(32);
+        std::vector<int32_t> dep(32);
+        int64_t m = 0;
+        const int L = mhnsw_reachability(Graph->handle(), mem.data(), rea.data(), dep.data(), 32, &m);
+        if (L < 0) return {r, make_error(L, Graph->handle())};
+        std::vector<int64_t> img((size_t)m + 1);
+        const int rc = mhnsw_unreachable_keys(Graph->handle(), img.data(), m);
+        if (rc < 0) return {r, make_error(rc, Graph->handle())};
+        img.resize((size_t)m);
+        r.members.assign(mem.begin(), mem.begin() + L);
+        r.reached.assign(rea.begin(), rea.begin() + L);
+        r.depth.assign(dep.begin(), dep.begin() + L);
+        r.unreachable_keys = Graph->DecodeKeys(img);
+        return {r, {}};
+    }
+
+    // relinks the unreachable layer-0 keys once -> {unreachable before, unreachable after}
+    // (the second is whatever the relinked graph gives: not necessarily 0)
+    std::pair<std::pair<int64_t, int64_t>, Error> Repair() {
+        auto before = Reachability();
+        if (before.second) return {{0, 0}, before.second};
+        const int64_t nb = (int64_t)before.first.unreachable_keys.size();
+        if (nb == 0) return {{0, 0}, {}};
+        auto rl = Graph->Relink(before.first.unreachable_keys);
+        if (rl.second) return {{nb, nb}, rl.second};
+        auto after = Reachability();
+        return {{nb, (int64_t)after.first.unreachable_keys.size()}, after.second};
+    }
 };
 
 // graph.go:340-348

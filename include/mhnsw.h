@@ -493,6 +493,81 @@ int mhnsw_update_device(mhnsw_index *h, const int64_t *keys, const float *d_vecs
 /* edge distances as stored: layout of mhnsw_export's adj ([L*N*cap]), 0 where adj is -1 */
 int mhnsw_export_edge_dist(mhnsw_index *h, float *adjd, int cap);
 
+/* ---- Relink: mhnsw_update with each found row's stored vector ----
+ * The graph around the found rows is detached and rebuilt exactly as an update
+ * with their own vectors would do it -- the same export, stored edge
+ * distances, out_found and "last_update_*" options, bit for bit -- but no
+ * vector is sent, written or converted: the overwrite step is skipped.  The
+ * remedy for rows that mhnsw_reachability reports.  Chunking, refusals,
+ * messages and exclusivity are mhnsw_update's; on a FLAT handle the call only
+ * fills out_found. */
+int mhnsw_relink(mhnsw_index *h, const int64_t *keys, int64_t n, uint8_t *out_found);
+
+/* ---- Analyzer (analyzer.go): quality metrics, degree histogram, hops, reachability ----
+ * Graph inspection on the device: the calls read `deg` and `adj` only (and the
+ * vectors of at most 100 sample rows), never a copy of the store.  They are
+ * read-only: they hold the handle's lock shared, first wait for the last
+ * enqueued *_device search as a mutation does, and serialise among themselves.
+ * A row is a live member of layer l when its deg there is not -2 and it is not
+ * deleted.  Every walk follows every stored edge (positions below deg, ids
+ * >= 0), through deleted rows too; an id outside the store is skipped and the
+ * call fails with MHNSW_EINTERNAL, "out-of-range node id in adjacency (graph
+ * corrupt)".  A handle with a replaced or re-added key fails every call with
+ * MHNSW_EUNSUPPORTED (the reference's BFS marks visits by key, the engine by
+ * row); a FLAT handle fails all but the histogram with MHNSW_EUNSUPPORTED,
+ * "analyzer needs a compat or batch (build_mode 0 or 1) handle".  Rows of up
+ * to 255 neighbours.  Read-only option: "last_analyzer_scratch_bytes" (device
+ * memory the calls keep: about 14 bytes per row of capacity for reachability,
+ * 52 for hops). */
+
+/* analyzer.go:69-90 GraphQualityMetrics */
+typedef struct mhnsw_quality {
+    int64_t node_count;          /* live layer-0 rows */
+    double avg_connectivity;     /* analyzer.go:93-109: sum of their deg (below 0: 0) / node_count, the sum exact */
+    double connectivity_std_dev; /* analyzer.go:112-130, see below */
+    double distortion_ratio;     /* analyzer.go:135-189, see below */
+    double layer_balance;        /* analyzer.go:245-279, on the host with pow() of libm (Go's math.Pow may differ
+                                    in the last bit) */
+    int64_t graph_height;        /* len(layers): mhnsw_num_layers */
+} mhnsw_quality;
+/* Analyzer.QualityMetrics (analyzer.go:51-67); all zero without layers.
+ * connectivity_std_dev = sqrt(sum_d hist[d] (d - avg)^2 / node_count) in
+ * double, d ascending over the exact layer-0 degree histogram (Go sums per
+ * node in map order, which is random: this order is the engine's policy).
+ * distortion_ratio: 0 below 10 live layer-0 rows; else the sample is the first
+ * min(100, node_count) live layer-0 rows in ascending row id (Go takes what its
+ * map yields first), and over the pairs i < j in that nested order with
+ * h = hops(sample[i] -> sample[j], depth 10) > 0 and a finite canonical
+ * distance a (q = sample[i]'s vector, X = sample[j]'s: the bits of
+ * mhnsw_distance) the mean of double(h) / double(a), summed in pair order (a
+ * zero distance gives +Inf, as in Go); 0 without such a pair. */
+int mhnsw_quality_metrics(mhnsw_index *h, mhnsw_quality *out);
+/* out[d], d < 64: live members of `layer` with degree d (below 0 counts as 0): the histogram
+ * behind analyzer.go:93-130.  MHNSW_EUNSUPPORTED when a member has more than 63 neighbours. */
+int mhnsw_degree_histogram(mhnsw_index *h, int layer, int64_t *out);
+/* estimateGraphDistance (analyzer.go:193-240) for every ordered pair of n keys:
+ * out[i * n + j] = edges on the shortest directed layer-0 path keys[i] ->
+ * keys[j], 0 for i == j, -1 when none of at most max_depth edges exists (the
+ * reference's fixed limit is 10).  1 <= n <= 128 (more: MHNSW_EUNSUPPORTED,
+ * "hops supports at most 128 keys"), 1 <= max_depth <= 64; a key without a
+ * live layer-0 row or a repeated key is MHNSW_EINVAL.  Arguments are checked
+ * before the handle is used. */
+int mhnsw_hops(mhnsw_index *h, const int64_t *keys, int n, int max_depth, int32_t *out);
+/* Which rows a search can ever visit.  T = the highest layer with a live
+ * member; R_T = the rows reachable in layer T from its entry (the export's
+ * entry[T], where every search starts); below, R_l = the rows reachable in
+ * layer l from R_(l+1)'s members of layer l.  Per layer l < max_layers (each
+ * pointer nullable): members[l] = live members, reached[l] = those in R_l,
+ * depth[l] = BFS levels run until the frontier emptied (0 without seeds).
+ * *out_unreachable (nullable) = members[0] - reached[0].  Returns the number
+ * of layers (>= 0) or an error.  mhnsw_unreachable_keys then copies the first
+ * min(cap, that count) keys of the last call's unreachable live layer-0 rows,
+ * in ascending row id.  Read-only option: "last_reach_ns" (device time, HIP
+ * events). */
+int mhnsw_reachability(mhnsw_index *h, int64_t *members, int64_t *reached, int32_t *depth, int max_layers,
+                       int64_t *out_unreachable);
+int mhnsw_unreachable_keys(mhnsw_index *h, int64_t *out_keys, int64_t cap);
+
 /* ---- DistanceFunc (distance.go:12-23): batched sweep of one query over n rows ---- */
 int mhnsw_distance(int metric, const float *q, const float *X, int64_t n, int dim, float *out);
 int mhnsw_distance_device(int metric, const float *d_q, const float *d_X, int64_t n, int dim, float *d_out,
