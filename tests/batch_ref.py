@@ -126,6 +126,17 @@ CASES["update-chunks"] = _case(n=2000, batch_max=40, script=(("add", 1, 1), ("up
                                reach=("update_chunks", "repaired"))
 CASES["update-top"] = _case(n=2000, script=(("add", 1, 1), ("update_top",)), reach=("update_chunks", "repaired"))
 CASES["update-all"] = _case(n=2000, script=(("add", 1, 1), ("update_all",)), reach=("update_chunks", "repaired"))
+# The link pass (k_batch_link<L, V, XW>) and the update's relink at the dimension configurations
+# the cases above leave out (engine.hpp pick_cfg; they run at d 48, and test_gpu_batch_link.py /
+# test_gpu_update.py at 768): one row per configuration, (d, metric, n, link batch,
+# build_expand).  build_expand 1 .. 4 is spread so that the link pass's units for widths 1 - 2
+# and 3 - 4 are both reached inside every group of configurations that has two dimensions here.
+for _d, _m, _n, _nb, _x in ((96, 1, 900, 150, 1), (200, 0, 900, 150, 3), (400, 1, 900, 150, 2), (1000, 0, 700, 120, 4),
+                            (1536, 1, 700, 120, 1), (2048, 0, 700, 120, 2), (3072, 1, 600, 100, 3),
+                            (4096, 0, 600, 100, 4)):
+    CASES[f"link-update-dim{_d}"] = _case(d=_d, n=_n, metrics=(_m,), build_expand=_x,
+                                          script=(("add_n", _n - _nb), ("link", _nb, 0), ("update_spread", 40)),
+                                          reach=("link_rows", "link_edges", "mutual", "update_chunks", "repaired"))
 
 
 # tests/golden/batch_build.npz: an engine-built graph after each of these calls
