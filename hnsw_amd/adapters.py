@@ -33,9 +33,12 @@ from .graph import CosineDistance, Graph, Node
 class ExactIndex:
     """hybrid/exact.go ExactIndex[K] on the GPU exact path."""
 
-    def __init__(self, distance=CosineDistance):
+    def __init__(self, distance=CosineDistance, wide: bool = False):
+        """wide: searches accept k up to 4096 (the handle option "exact_wide") instead of 256."""
         self.distance = distance
         self._g = Graph(M=16, Ml=0.25, EfSearch=20, Distance=distance, build_mode=BUILD_FLAT)
+        if wide:
+            self._g.set_option("exact_wide", 1)
 
     def Add(self, key, vector) -> None:  # exact.go:28-38
         self.BatchAdd([key], [vector])

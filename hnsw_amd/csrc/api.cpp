@@ -1291,6 +1291,13 @@ void mhnsw_destroy(mhnsw_index* h) {
     F(h->rgkeys.p);
     F(h->rgdist.p);
     F(h->rgoff.p);
+    F(h->wrad.p);
+    F(h->wdist.p);
+    F(h->wlims.p);
+    F(h->wshort.p);
+    F(h->wstat.p);
+    for (auto e : h->wev)
+        if (e) (void)hipEventDestroy(e);
     F(h->uids.p);
     F(h->d_repaired);
     F(h->an_bits.p);
@@ -1434,6 +1441,18 @@ int mhnsw_set_option(mhnsw_index* h, const char* name, int64_t v) {
     } else if (n == "range_force_fallback") {
         if (v < 0 || v > 1) return fail(h, MHNSW_EINVAL, "range_force_fallback must be 0 or 1");
         h->range_force_fallback = (int)v;
+    } else if (n == "exact_wide") {
+        if (v < 0 || v > 1) return fail(h, MHNSW_EINVAL, "exact_wide must be 0 or 1");
+        h->exact_wide = (int)v;
+    } else if (n == "exact_wide_min_k") {
+        if (v < 1) return fail(h, MHNSW_EINVAL, "exact_wide_min_k must be >= 1");
+        h->exact_wide_min_k = (int)std::min<int64_t>(v, 1 << 30);
+    } else if (n == "wide_force_fallback") {
+        if (v < 0 || v > 1) return fail(h, MHNSW_EINVAL, "wide_force_fallback must be 0 or 1");
+        h->wide_force_fallback = (int)v;
+    } else if (n == "wide_fallback_bytes") {
+        if (v < 1) return fail(h, MHNSW_EINVAL, "wide_fallback_bytes must be >= 1");
+        h->wide_fallback_bytes = v;
     } else if (n == "exact_kk") {
         h->exact_kk = (int)v;
     } else if (n == "exact_tile") {
@@ -1622,6 +1641,38 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
             hipMemcpy(st, h->rstat.p, sizeof st, hipMemcpyDeviceToHost) != hipSuccess)
             return MHNSW_EDEVICE;
         *v = (int64_t)st[n == "last_range_candidates" ? 0 : 1];
+    }
+    else if (n == "exact_wide") *v = h->exact_wide;
+    else if (n == "exact_wide_min_k") *v = h->exact_wide_min_k;
+    else if (n == "wide_force_fallback") *v = h->wide_force_fallback;
+    else if (n == "wide_fallback_bytes") *v = h->wide_fallback_bytes;
+    // read-only, of the last exact search: the queries that took the wide path (0: none did), the
+    // hit-buffer entries per query and the sample rank J it chose, and from the device (waits for
+    // the search) the queries the fallback select answered and the hits that reached the sort
+    else if (n == "last_wide_queries") *v = h->wide_queries;
+    else if (n == "last_wide_room") *v = h->wide_queries ? h->wide_room : 0;
+    else if (n == "last_wide_rank") *v = h->wide_queries ? h->wide_rank : 0;
+    else if (n == "last_wide_fallback_queries" || n == "last_wide_hits") {
+        unsigned long long st[2] = {0, 0};
+        if (h->wide_queries &&
+            ((h->scr_valid && hipEventSynchronize(h->scr_ev) != hipSuccess) ||
+             hipMemcpy(st, h->wstat.p, sizeof st, hipMemcpyDeviceToHost) != hipSuccess))
+            return MHNSW_EDEVICE;
+        *v = (int64_t)st[n == "last_wide_fallback_queries" ? 0 : 1];
+    }
+    else if (n.rfind("last_wide_", 0) == 0) {
+        // read-only: the last timed wide exact search's stages (HIP events): of its first chunk of
+        // queries the sample pass, the radius select and the range stages (threshold .. sweep); of
+        // the whole call the cut (sort + emit) and the fallback select
+        static const char* const stage[5] = {"sample", "radius", "range", "emit", "fallback"};
+        static const int first[5] = {0, 1, 2, 4, 5};
+        int i = 0;
+        while (i < 5 && n != std::string("last_wide_") + stage[i] + "_ns") ++i;
+        float ms = 0.f;
+        if (i == 5 || !h->wide_queries || !h->have_wide_timing || hipEventSynchronize(h->wev[first[i] + 1]) != hipSuccess ||
+            hipEventElapsedTime(&ms, h->wev[first[i]], h->wev[first[i] + 1]) != hipSuccess)
+            return MHNSW_EINVAL;
+        *v = (int64_t)std::llround((double)ms * 1e6);
     }
     else if (n.rfind("last_range_", 0) == 0) {
         // read-only: the last exact-mode range search's stages (HIP events): of its first chunk of
@@ -1812,7 +1863,7 @@ int mhnsw_search_filtered_exact(mhnsw_index* h, const float* queries, int64_t B,
                                           out_n, h->stream, false);
     // every argument error before the first pass writes a result
     if (k <= 0) return fail(h, MHNSW_EK, "k must be greater than 0, got %d", k);
-    if (k > 256) return fail(h, MHNSW_EUNSUPPORTED, "exact mode supports k <= 256");
+    if (int r = exact_k_check(h, k)) return r;
     for (const auto& [f, rows] : groups)
         if (f < -1 || (f >= 0 && (f >= (int)h->filters.size() || !h->filters[f].used)))
             return fail(h, MHNSW_EINVAL, "unknown filter %d", f);

@@ -477,6 +477,9 @@ int launch_range_sweep(const RangeArgs& a, int64_t N, int nseg, int64_t seglen, 
                        hipStream_t s);
 int launch_range_scan(const int32_t* cnt, int64_t B, int64_t* lims, int32_t* cursor, hipStream_t s);
 int range_sort_temp_bytes(int64_t hcap, int64_t B, size_t* bytes);
+int launch_range_order(const unsigned long long* hits, unsigned long long* sorted, int64_t hcap, const int64_t* lims,
+                       int64_t B, int64_t cap, uint32_t* seg_b, uint32_t* seg_e, void* temp, size_t temp_bytes,
+                       hipStream_t s);  // the sort alone (the wide exact search cuts the segments itself)
 int launch_range_order_emit(const unsigned long long* hits, unsigned long long* sorted, int64_t hcap,
                             const int64_t* lims, int64_t B, int64_t cap, uint32_t* seg_b, uint32_t* seg_e, void* temp,
                             size_t temp_bytes, const GraphDev& g, int64_t* keys, float* dist, hipStream_t s);
@@ -486,5 +489,48 @@ int launch_range_place(const int64_t* src_keys, const float* src_dist, const int
 // beam mode: the beam lists bk / bd / bn [B * ef] cut by the radius -> lims, keys, dist
 int launch_range_beam(const int64_t* bk, const float* bd, const int32_t* bn, int ef, const float* radius, int64_t B,
                       int32_t* cnt, int64_t* lims, int64_t cap, int64_t* keys, float* dist, hipStream_t s);
+
+// ---- wide exact search (wide.hip): exact top-k past k 256 through the range pipeline ----
+// One chunk of queries: the J-th smallest of each query's ns sample scores (launch_h1_sample's
+// compact matrix) as a distance radius, widened by the certificate's score error; NaN where no
+// estimate can be made (force, ns < J, a zero query under cosine, a query outside the fp16
+// bound -- qinv NaN --, a J-th score that is not finite).
+struct WideRadiusArgs {
+    const float* scores;  // [B * ldS]
+    int64_t ldS, ns;
+    int J;
+    int metric;
+    int force;            // test option wide_force_fallback: every radius NaN
+    const float* qnorm;   // [B]
+    const float* qinv;    // [B] (read only when ns >= J)
+    CertArgs c;           // eps_cos / eps_dot / c_l2 / xmax / xerr / qerr
+    int64_t B;
+    float* radius;        // [B] out
+};
+int launch_wide_radius(const WideRadiusArgs& a, hipStream_t s);
+// The cut, over the whole call: query b's sorted hits are sorted[lims[b] .. lims[b + 1]) when
+// lims[b] < cap (else it wrote none).  >= k of them: the first k -> [b, :k], n[b] = k.  Fewer:
+// b joins shortq (stat[0] counts the list; stat[1] += the hits that reached the sort).
+struct WideEmitArgs {
+    const unsigned long long* sorted;
+    const int64_t* lims;  // [B + 1]
+    int64_t B, cap;
+    int k;                // <= 4096
+    const int64_t* keys;  // row -> key
+    uint32_t capn;
+    int64_t* out_keys;    // [B * k]
+    float* out_dist;      // [B * k]
+    int32_t* out_n;       // [B]
+    int32_t* out_ids;     // [B * k] (nullable)
+    int32_t* shortq;      // [B]
+    unsigned long long* stat;  // [2]
+};
+int launch_wide_emit(const WideEmitArgs& a, hipStream_t s);
+// The short queries [g0, g0 + gn) of the list (none there: both kernels exit at once): the
+// canonical distance of rows [0, N) of the index into wd [gn * ldW] (rows g.dead masks are
+// skipped, as NaN distances are), then per query the min(k, qualifying) smallest by
+// (distance, row id), sorted and written to [b, :k] with n[b]; Q: the call's padded queries.
+int launch_wide_fallback(const float* Q, const GraphDev& g, int64_t N, const WideEmitArgs& a, int64_t g0, int64_t gn,
+                         float* wd, int64_t ldW, int lpr, int vpl, hipStream_t s);
 
 }  // namespace mh

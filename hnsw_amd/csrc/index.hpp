@@ -270,6 +270,23 @@ struct mhnsw_index {
     int64_t range_total = -1;  // hits the last host-pointer range search left in rkeys / rdist (-1: none)
     bool have_range_stats = false;
     bool have_range_timing = false;  // fxev holds an exact-mode range search's stage marks (options "last_range_*_ns")
+    // wide exact search (wide.hip; search_host.cpp wide_exact): exact mode past k 256 through the
+    // range pipeline.  The call's radii, prefix, short-query list and counters {short queries,
+    // hits that reached the sort}, the fallback's distance rows; stage marks of the last timed
+    // call (created on first use): sample start, sample end, radius end, the first chunk's range
+    // stages end, sort start, cut end, fallback end (options "last_wide_*_ns")
+    int exact_wide = 0;            // 1: exact mode accepts k <= 4096
+    int exact_wide_min_k = 257;    // the smallest k that takes the wide path (k > 256 always does)
+    int wide_force_fallback = 0;   // test option: every query is answered by the fallback select
+    int64_t wide_fallback_bytes = (int64_t)1 << 30;  // the fallback's distance rows: queries per group = this / (4 rows)
+    DevBuf<float> wrad, wdist;
+    DevBuf<int64_t> wlims;
+    DevBuf<int32_t> wshort;
+    DevBuf<unsigned long long> wstat;
+    hipEvent_t wev[7] = {};
+    bool have_wide_timing = false;
+    int64_t wide_queries = 0;      // queries of the last exact search that took the wide path
+    int64_t wide_room = 0, wide_rank = 0;  // ... its hit-buffer entries per query and its sample rank J
     // compaction (mhnsw_compact): rows per staged chunk (measured default: DESIGN.md §6 "Compaction"),
     // and of the last call its event pair, device allocations and dropped edges to deleted rows
     int64_t compact_stage_rows = 16384;
@@ -356,6 +373,7 @@ int beam_vis_entries(const mhnsw_index* h);
 int drain(mhnsw_index* h);
 int search_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int mode, int ef, const int64_t* entry_key, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool timing, int32_t* out_ids = nullptr, bool sticky = false);
 int device_error(mhnsw_index* h, int err);
+int exact_k_check(mhnsw_index* h, int k);  // exact mode's limit on k (256, or 4096 with "exact_wide")
 void reset_graph(mhnsw_index* h);
 constexpr int MHNSW_MAX_FILTERS = 1024;
 void drop_filters(mhnsw_index* h);

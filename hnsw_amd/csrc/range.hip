@@ -403,17 +403,25 @@ int range_sort_temp_bytes(int64_t hcap, int64_t B, size_t* bytes) {
     return e == hipSuccess ? 0 : -1;
 }
 
-// hits[seg] sorted into sorted[seg] per query, then the keys and distances below cap
-int launch_range_order_emit(const unsigned long long* hits, unsigned long long* sorted, int64_t hcap,
-                            const int64_t* lims, int64_t B, int64_t cap, uint32_t* seg_b, uint32_t* seg_e, void* temp,
-                            size_t temp_bytes, const GraphDev& g, int64_t* keys, float* dist, hipStream_t s) {
+// hits[seg] sorted into sorted[seg] per query
+int launch_range_order(const unsigned long long* hits, unsigned long long* sorted, int64_t hcap, const int64_t* lims,
+                       int64_t B, int64_t cap, uint32_t* seg_b, uint32_t* seg_e, void* temp, size_t temp_bytes,
+                       hipStream_t s) {
     if (B <= 0) return 0;
     if (hcap <= 0 || hcap > (int64_t)0x7fffffff || B > (int64_t)0x7fffffff) return -4;
     hipLaunchKernelGGL(k_range_segs, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, lims, B, cap, seg_b, seg_e);
     if (hipGetLastError() != hipSuccess) return -1;
     const hipError_t e = rocprim::segmented_radix_sort_keys(temp, temp_bytes, hits, sorted, (unsigned)hcap, (unsigned)B,
                                                             (const uint32_t*)seg_b, (const uint32_t*)seg_e, 0u, 64u, s);
-    if (e != hipSuccess) return -1;
+    return e == hipSuccess ? 0 : -1;
+}
+
+// ... then the keys and distances below cap
+int launch_range_order_emit(const unsigned long long* hits, unsigned long long* sorted, int64_t hcap,
+                            const int64_t* lims, int64_t B, int64_t cap, uint32_t* seg_b, uint32_t* seg_e, void* temp,
+                            size_t temp_bytes, const GraphDev& g, int64_t* keys, float* dist, hipStream_t s) {
+    if (B <= 0) return 0;
+    if (const int r = launch_range_order(hits, sorted, hcap, lims, B, cap, seg_b, seg_e, temp, temp_bytes, s)) return r;
     if (cap <= 0) return 0;
     const int64_t blocks = std::min<int64_t>((cap + 255) / 256, 8192);
     hipLaunchKernelGGL(k_range_emit, dim3((unsigned)blocks), dim3(256), 0, s, sorted, lims + B, cap, g.keys, g.capn, keys,

@@ -308,6 +308,26 @@ static int exact_skipped(mhnsw_index* h, hipStream_t s, const uint8_t*& xdead) {
     return 0;
 }
 
+// the sample pass's shape over N rows: every stride-th full row tile, nsamp of them (h1: the fused path runs)
+static void sample_shape(const mhnsw_index* h, int64_t N, bool h1, int& stride, int64_t& nsamp) {
+    const int64_t nnt = (N + H1_BN - 1) / H1_BN;
+    stride = (int)std::max<int64_t>(1, std::min<int64_t>(128, (nnt + h->exact_sample - 1) / h->exact_sample));
+    nsamp = h1 ? ((N / H1_BN) - 1) / stride + 1 : 0;
+}
+
+// Exact mode's limit on k, and whether the search takes the wide path (option "exact_wide":
+// every k past 256, and the k from "exact_wide_min_k" up)
+static int exact_k_limit(mhnsw_index* h, int k, bool& wide) {
+    wide = h->exact_wide && (k > 256 || k >= h->exact_wide_min_k);
+    if (h->exact_wide && k > 4096) return fail(h, MHNSW_EUNSUPPORTED, "exact mode supports k <= 4096");
+    if (!h->exact_wide && k > 256) return fail(h, MHNSW_EUNSUPPORTED, "exact mode supports k <= 256");
+    return 0;
+}
+int exact_k_check(mhnsw_index* h, int k) {
+    bool wide;
+    return exact_k_limit(h, k, wide);
+}
+
 // the exact path's workspace, the rows it skips and the certificate constants
 // (expect > 0, a range search: the regions and sub-buckets are sized for that many passing
 // rows per query over the whole index instead of J over the sample)
@@ -361,8 +381,9 @@ static int exact_prepare(mhnsw_index* h, const SearchCall& c, const RowSet& rs, 
     const int ev = h1_effective_variant(h->exact_tile, h->pitch, std::max<int64_t>(qc, rs.ld));
     const int bm = h1_tile_bm(ev);
     const int64_t nnt = (N + H1_BN - 1) / H1_BN, nqt = (qc + bm - 1) / bm;
-    const int stride = (int)std::max<int64_t>(1, std::min<int64_t>(128, (nnt + h->exact_sample - 1) / h->exact_sample));
-    const int64_t nsamp = h1 ? ((N / H1_BN) - 1) / stride + 1 : 0;  // sampled full tiles
+    int stride;
+    int64_t nsamp;  // sampled full tiles
+    sample_shape(h, N, h1, stride, nsamp);
     const int J = stride < 8 ? kk : h->exact_thr_rank > 0 ? std::min(kk, std::max(k, h->exact_thr_rank)) : std::max(k, kk / 8);
     // the score workspace: every (query, row) score (precisions 0-2, and their
     // fallback), or only the sample's (fused path: its fallback streams distances
@@ -632,11 +653,14 @@ static int exact_run(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan)
     return 0;
 }
 
+static int wide_exact(mhnsw_index* h, SearchCall& c, const RowSet& rset);
+
 // mhnsw_search*, and the candidate search of mhnsw_search_negatives
 static int search_plain(mhnsw_index* h, SearchCall& c, int mode, int ef, const int64_t* entry_key) {
     int r = validate(h);
     if (r) return r;
     h->have_gemm_timing = false;  // last_gemm_ns describes this search or none
+    if (mode == MHNSW_MODE_EXACT) h->wide_queries = 0;  // last_wide_* describe this exact search, however it ends
     if ((r = check_args(h, c, mode))) return r;
     if (c.B <= 0) return 0;
     if (!h->layers_exist || live_count(h) == 0) return zero_counts(h, c);
@@ -651,6 +675,12 @@ static int search_plain(mhnsw_index* h, SearchCall& c, int mode, int ef, const i
     if ((r = stage(h, c))) return r;
     if (mode == MHNSW_MODE_EXACT) {
         ExactPlan plan;
+        bool wide;
+        if ((r = exact_k_limit(h, c.k, wide))) return r;
+        if (wide) {  // (always at precision 3, as the range search)
+            r = wide_exact(h, c, RowSet{h->n, h->capn, 3, nullptr, nullptr, 0});
+            return r ? r : finish(h, c);
+        }
         const RowSet every{h->n, h->capn, h->exact_precision, nullptr, nullptr, 0};
         if (!(r = exact_prepare(h, c, every, plan))) r = exact_run(h, c, plan);
     } else {
@@ -761,9 +791,11 @@ static int filter_rowset(mhnsw_index* h, hipStream_t s, int filter, int precisio
 // rows as a gathered row set.  The host's mirror of the bitmap sizes the launches (the same
 // words and skipped rows the compaction kernel counts).  Always timed, with stage marks.
 static int search_filtered_exact(mhnsw_index* h, SearchCall& c, int filter) {
+    h->wide_queries = 0;  // last_wide_* describe this exact search, however it ends
     int r = validate(h);
     if (r || (r = check_args(h, c, MHNSW_MODE_EXACT))) return r;
-    if (c.k > 256) return fail(h, MHNSW_EUNSUPPORTED, "exact mode supports k <= 256");
+    bool wide;
+    if ((r = exact_k_limit(h, c.k, wide))) return r;
     if (filter < 0 || filter >= (int)h->filters.size() || !h->filters[filter].used)
         return fail(h, MHNSW_EINVAL, "unknown filter %d", filter);
     if (c.B <= 0) return 0;
@@ -772,13 +804,18 @@ static int search_filtered_exact(mhnsw_index* h, SearchCall& c, int filter) {
     if (!h->layers_exist || live_count(h) == 0) return zero_counts(h, c);
     // without an fp16 row plane (exact_precision 0 or 1) the call scores at precision 3
     RowSet rset;
-    if ((r = filter_rowset(h, c.s, filter, h->exact_precision >= 2 ? h->exact_precision : 3, rset))) return r;
+    const int precision = wide ? 3 : h->exact_precision >= 2 ? h->exact_precision : 3;
+    if ((r = filter_rowset(h, c.s, filter, precision, rset))) return r;
     if (rset.n == 0) {  // nothing allowed: no row, no error
         h->stats_host[6] += c.B;
         h->have_timing = false;
         return zero_counts(h, c);
     }
     if ((r = stage(h, c))) return r;
+    if (wide) {
+        r = wide_exact(h, c, rset);
+        return r ? r : finish(h, c);
+    }
     ExactPlan plan;
     if (!(r = exact_prepare(h, c, rset, plan))) r = exact_run(h, c, plan);
     return r ? r : finish(h, c);
@@ -833,12 +870,29 @@ struct RangeRows {
 // The plan's row set is every row of the index, or a filter's allowed rows: then the id list
 // is compacted and the rows' plane gathered first (as exact_run does), the GEMM runs over the
 // gathered plane, refine maps its positions to row ids and the sweep walks the id list.
-static int range_exact(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan, const RangeOut& o) {
+// A wide exact search (wide_exact) runs the same stages with two differences: each chunk's
+// radii are estimated first (the sample pass and k_wide_radius write them into o.radius's
+// buffer), and the sorted segments are cut at k into the call's [B, k] outputs, the short
+// queries answered by the fallback select, instead of being emitted whole.
+struct WideRun {
+    int k, J;             // the call's k; the rank of the sample score that becomes the radius
+    float* radius;        // [B] == o.radius
+    int64_t* dk;          // the call's outputs on the device
+    float* dd;
+    int32_t* dn;
+    int32_t* out_ids;
+};
+static int wide_cut(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan, const RangeOut& o, const WideRun& w,
+                    int64_t hcap, size_t tmp_bytes);
+
+static int range_exact(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan, const RangeOut& o,
+                       const WideRun* w = nullptr) {
     int r;
     hipStream_t s = c.s;
     const RowSet& rs = plan.rs;
     const bool gathered = rs.ids != nullptr;
-    const bool fused = plan.h1 && !h->range_force_fallback;
+    const int force = w ? 0 : h->range_force_fallback;  // (the range search's test option is not the wide search's)
+    const bool fused = plan.h1 && !force;
     const int64_t qc = plan.qc, B = c.B;
     const int64_t hcap = o.cap + rs.n;  // a query that starts below cap holds all its hits (<= the set's rows)
     if (hcap > (int64_t)0x7fffffff)
@@ -915,9 +969,55 @@ static int range_exact(mhnsw_index* h, const SearchCall& c, const ExactPlan& pla
             HIPCHK(h, hipMemsetAsync(h->qerr.p, 0, sizeof(float), s));
             LCHK(h, launch_split_h16(ra.Q, 0, nb, h->pitch, qc, h->qsplit.p, nullptr, h->qinv.p, h->qerr.p, s));
         }
+        if (w) {
+            // 0. (wide exact search) the sample pass as exact_run runs it, then the radii
+            const bool wmark = c.timing && q0 == 0;
+            if (wmark) HIPCHK(h, hipEventRecord(h->wev[0], s));
+            const bool sample = fused && !h->wide_force_fallback && plan.nsamp * H1_BN >= w->J;
+            if (sample) {
+                ExactArgs as{};
+                as.X = h->vecs;
+                as.xnorm = xnorm;
+                as.dead = sdead;
+                as.N = rs.n;
+                as.Q = ra.Q;
+                as.qnorm = c1.qnorm;
+                as.B = nb;
+                as.pitch = h->pitch;
+                as.dim = h->dim;
+                as.metric = h->metric;
+                as.scores = h->scores.p;
+                as.Xh = Xh;
+                as.Xl = Xh + (size_t)ldX * h->pitch;
+                as.ldXs = ldX;
+                as.Qh = h->qsplit.p;
+                as.Ql = h->qsplit.p + (size_t)qc * h->pitch;
+                as.ldQs = qc;
+                as.xinv = xinv;
+                as.qinv = h->qinv.p;
+                as.tile_stride = plan.stride;
+                as.nsample_tiles = plan.nsamp;
+                as.ldS = plan.nsamp * H1_BN;
+                LCHK(h, launch_h1_sample(as, plan.ev, s));
+            }
+            if (wmark) HIPCHK(h, hipEventRecord(h->wev[1], s));
+            WideRadiusArgs wr{};
+            wr.scores = h->scores.p;
+            wr.ldS = plan.nsamp * H1_BN;
+            wr.ns = sample ? plan.nsamp * H1_BN : 0;
+            wr.J = w->J;
+            wr.metric = h->metric;
+            wr.force = h->wide_force_fallback;
+            wr.qnorm = c1.qnorm;
+            wr.qinv = h->qinv.p;
+            wr.c = c1;
+            wr.B = nb;
+            wr.radius = w->radius + q0;
+            LCHK(h, launch_wide_radius(wr, s));
+            if (wmark) HIPCHK(h, hipEventRecord(h->wev[2], s));
+        }
         // 1. the radius as the score threshold, and each query's path
-        LCHK(h, launch_range_thr(ra, c1.qnorm, fused ? h->qinv.p : nullptr, c1,
-                                 h->range_force_fallback ? -1 : fused ? 1 : 0, h->rthr.p, s));
+        LCHK(h, launch_range_thr(ra, c1.qnorm, fused ? h->qinv.p : nullptr, c1, force ? -1 : fused ? 1 : 0, h->rthr.p, s));
         if (fused) {
             // 2. the filter GEMM and the per-query buckets, as the top-k search runs them
             ExactArgs a{};
@@ -974,15 +1074,127 @@ static int range_exact(mhnsw_index* h, const SearchCall& c, const ExactPlan& pla
         if (fused) LCHK(h, launch_range_gather(ra, s));
         LCHK(h, launch_range_sweep(ra, rs.n, plan.nseg, plan.seglen, true, h->lpr, h->vpl, s));
         if (mark0) HIPCHK(h, hipEventRecord(h->fxev[3], s));
+        if (w && mark0) HIPCHK(h, hipEventRecord(h->wev[3], s));
     }
     if (c.timing) HIPCHK(h, hipEventRecord(h->fxev[4], s));
     // 5. order each query's segment by (distance, row id) and emit
-    LCHK(h, launch_range_order_emit(h->rhits.p, h->rhits.p + hcap, hcap, o.lims, B, o.cap, h->rseg.p, h->rseg.p + B,
-                                    h->rtmp.p, tmp_bytes, plan.g, o.keys, o.dist, s));
+    if (w) {
+        if ((r = wide_cut(h, c, plan, o, *w, hcap, tmp_bytes))) return r;
+    } else {
+        LCHK(h, launch_range_order_emit(h->rhits.p, h->rhits.p + hcap, hcap, o.lims, B, o.cap, h->rseg.p, h->rseg.p + B,
+                                        h->rtmp.p, tmp_bytes, plan.g, o.keys, o.dist, s));
+    }
     if (c.timing) HIPCHK(h, hipEventRecord(h->fxev[5], s));
     h->have_range_timing = c.timing;
     if (fused && h1_timing_diag(plan.ev))
         return fail(h, MHNSW_EUNSUPPORTED, "exact_tile %d is a timing diagnostic: no results", h->exact_tile);
+    return 0;
+}
+
+// ---- wide exact search: exact mode past k 256 (wide.hip; DESIGN.md "Wide exact search") ----
+// The rank J of the sample score that becomes the radius, for a sample that holds the fraction
+// f of the rows: the smallest J with P(Poisson(k f) >= J) <= 1e-5, at most k (wide.hip's
+// header has the argument).  The pmf is summed in log space (k f reaches 4096).
+static int wide_rank_for(int k, double f) {
+    if (f >= 1.0) return k;
+    const double lam = k * f, p = 1e-5;
+    double cdf = 0.0;
+    for (int j = 0; j < k; ++j) {  // cdf = P(X <= j - 1) here
+        if (1.0 - cdf <= p) return std::max(j, 1);
+        cdf += std::exp(-lam + j * std::log(lam) - std::lgamma(j + 1.0));
+    }
+    return k;
+}
+
+// Step 4 and 5 of a wide exact search, over the whole call: the segment sort, the cut at k,
+// the fallback select for the short queries a group at a time (a group with no listed query
+// exits at once, so nothing here waits for the list's length).
+static int wide_cut(mhnsw_index* h, const SearchCall& c, const ExactPlan& plan, const RangeOut& o, const WideRun& w,
+                    int64_t hcap, size_t tmp_bytes) {
+    int r;
+    hipStream_t s = c.s;
+    const int64_t B = c.B;
+    const int64_t ldW = (h->n + 63) / 64 * 64;
+    const int64_t G = std::max<int64_t>(1, std::min<int64_t>(B, h->wide_fallback_bytes / (4 * ldW)));
+    if ((r = ensure_buf(h, h->wdist, (size_t)G * ldW))) return r;
+    if (c.timing) HIPCHK(h, hipEventRecord(h->wev[4], s));
+    LCHK(h, launch_range_order(h->rhits.p, h->rhits.p + hcap, hcap, o.lims, B, o.cap, h->rseg.p, h->rseg.p + B,
+                               h->rtmp.p, tmp_bytes, s));
+    WideEmitArgs e{};
+    e.sorted = h->rhits.p + hcap;
+    e.lims = o.lims;
+    e.B = B;
+    e.cap = o.cap;
+    e.k = w.k;
+    e.keys = plan.g.keys;
+    e.capn = plan.g.capn;
+    e.out_keys = w.dk;
+    e.out_dist = w.dd;
+    e.out_n = w.dn;
+    e.out_ids = w.out_ids;
+    e.shortq = h->wshort.p;
+    e.stat = h->wstat.p;
+    LCHK(h, launch_wide_emit(e, s));
+    if (c.timing) HIPCHK(h, hipEventRecord(h->wev[5], s));
+    // the short queries: every row of the index the call's mask lets through (a filter's allowed
+    // rows, as exact_run's gathered fallback reads them; else the rows the exact search skips)
+    GraphDev gm = plan.g;
+    if (plan.rs.ids) gm.dead = h->fxmask.p;
+    for (int64_t g0 = 0; g0 < B; g0 += G)
+        LCHK(h, launch_wide_fallback(h->qpad.p, gm, h->n, e, g0, std::min(G, B - g0), h->wdist.p, ldW, h->lpr, h->vpl, s));
+    if (c.timing) HIPCHK(h, hipEventRecord(h->wev[6], s));
+    h->have_wide_timing = c.timing;
+    return 0;
+}
+
+// Exact mode at k up to 4096 over a row set (every row, or a filter's allowed rows): the range
+// pipeline at radii estimated from the sample, cut at k (range_exact with a WideRun).  c is
+// staged.  Room: the radius is the J-th smallest of a sample of fraction f, so the rows within
+// it number about J / f with a standard deviation of sqrt(J (1 - f)) / f; the hit buffer holds
+// (J + 4 sqrt(J (1 - f))) / f per query plus an eighth (the radius is widened by the score
+// error) and 64, at most the row count.  Regions and sub-buckets are sized for the same number.
+static int wide_exact(mhnsw_index* h, SearchCall& c, const RowSet& rset) {
+    int r;
+    hipStream_t s = c.s;
+    const int k = c.k;
+    const int64_t B = c.B, N = rset.n;
+    for (auto& e : h->wev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    h->have_range_stats = false;
+    h->have_range_timing = false;
+    h->have_rs_timing = false;
+    h->have_fx_timing = false;
+    h->have_wide_timing = false;
+    if (B > (int64_t)0x7fffffff) return fail(h, MHNSW_EUNSUPPORTED, "exact mode supports B < 2^31");
+    int stride;
+    int64_t nsamp;
+    sample_shape(h, N, N >= H1_BN, stride, nsamp);
+    const double f = N > 0 ? std::min(1.0, (double)(nsamp * H1_BN) / (double)N) : 0.0;
+    const int J = f > 0.0 ? wide_rank_for(k, f) : k;
+    int64_t room = 1;  // (no estimate: every query is short, and nothing reaches the hit buffer)
+    if (f > 0.0 && J <= nsamp * H1_BN && !h->wide_force_fallback) {
+        const double hits = (J + 4.0 * std::sqrt(J * (1.0 - f))) / f;
+        room = std::min<int64_t>(N, (int64_t)std::ceil(hits * 1.125) + 64);
+    }
+    const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(B * room, (int64_t)0x7fffffff - N - 1));
+    SearchCall c1 = c;
+    c1.k = 1;  // (the exact path's workspace sizing, as the range search)
+    ExactPlan plan;
+    if ((r = exact_prepare(h, c1, rset, plan, room))) return r;
+    if ((r = ensure_buf(h, h->wrad, (size_t)B)) || (r = ensure_buf(h, h->wlims, (size_t)B + 1)) ||
+        (r = ensure_buf(h, h->wshort, (size_t)B)) || (r = ensure_buf(h, h->wstat, 2)) || (r = ensure_buf(h, h->rstat, 2)))
+        return r;
+    HIPCHK(h, hipMemsetAsync(h->wstat.p, 0, 16, s));
+    HIPCHK(h, hipMemsetAsync(h->rstat.p, 0, 16, s));
+    HIPCHK(h, hipMemsetAsync(h->wlims.p, 0, 8, s));
+    if (c.timing) HIPCHK(h, hipEventRecord(h->ev0, s));
+    const RangeOut o{h->wrad.p, cap, h->wlims.p, nullptr, nullptr};
+    const WideRun w{k, J, h->wrad.p, c.dk, c.dd, c.dn, c.out_ids};
+    if ((r = range_exact(h, c, plan, o, &w))) return r;
+    if (c.timing) HIPCHK(h, hipEventRecord(h->ev1, s));
+    h->wide_queries = B;
+    h->wide_room = room;
+    h->wide_rank = J;
     return 0;
 }
 

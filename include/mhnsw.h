@@ -215,7 +215,30 @@ int mhnsw_add_reached(const mhnsw_index *h, int64_t *reached);
  * MHNSW_MODE_BEAM takes 1 <= max(ef, k) <= 2048 (up to 512 the list is held in
  * registers, from 513 in LDS: the same search, bit-identical to the oracle's);
  * past 2048 the call fails with MHNSW_EUNSUPPORTED, "beam mode supports
- * max(ef,k) <= 2048". */
+ * max(ef,k) <= 2048".
+ * MHNSW_MODE_EXACT takes k <= 256 ("exact mode supports k <= 256"), and with
+ * the option "exact_wide" = 1 (default 0) k <= 4096 ("exact mode supports
+ * k <= 4096"): the wide exact search.  A search at k > 256, or at k >=
+ * "exact_wide_min_k" (default 257, any value >= 1), then runs the range
+ * search's pipeline at a per-query radius estimated from the sample pass (the
+ * J-th smallest sample score, J from a Poisson tail bound on k x the sampled
+ * fraction), cuts each query's sorted hits at k, and answers the queries whose
+ * radius held fewer than k rows -- or that got no room in the hit buffer -- by
+ * a select over the canonical distances of every row.  The results are the
+ * exact mode's: the k rows of smallest canonical distance by (distance, row
+ * id), the same skipped rows, NaN never returned, out_n[b] = min(k, rows
+ * available); always scored at precision 3.  The filtered exact calls below
+ * take the same path over a filter's allowed rows.  Options: "wide_fallback_bytes"
+ * (default 2^30: the fallback's distance rows, queries per group = this /
+ * (4 x rows)); test option "wide_force_fallback" (1: every query is answered by
+ * the fallback select).  Read-only, of the last exact search:
+ * last_wide_queries (the queries that took the wide path, 0: none),
+ * last_wide_fallback_queries, last_wide_hits (hits that reached the sort: over
+ * B x k it is the overshoot), last_wide_rank (J), last_wide_room (hit-buffer
+ * entries per query), and of a timed search last_wide_sample_ns,
+ * last_wide_radius_ns, last_wide_range_ns (first chunk of queries),
+ * last_wide_emit_ns (sort and cut) and last_wide_fallback_ns; the
+ * last_range_*_ns options then describe its range stages. */
 int mhnsw_search(mhnsw_index *h, const float *queries, int64_t B, int dim, int k, int mode, int ef,
                  const int64_t *entry_key, int64_t *out_keys, float *out_dist, int32_t *out_n);
 int mhnsw_search_device(mhnsw_index *h, const float *d_queries, int64_t B, int dim, int k, int mode, int ef,
@@ -274,14 +297,16 @@ int mhnsw_search_filtered_device(mhnsw_index *h, const float *d_queries, int64_t
  * stages on it (certificate and fallback included); nothing is kept between
  * calls.  With exact_precision 0 or 1, which keep no fp16 row plane, the call
  * scores at precision 3 (the results do not depend on the precision).  Works
- * in every build mode, MHNSW_BUILD_FLAT included.  k <= 256.
+ * in every build mode, MHNSW_BUILD_FLAT included.  k <= 256, or with the option
+ * "exact_wide" k <= 4096 (the wide exact search, see mhnsw_search).
  * mhnsw_search_filtered_exact: filter_of[b] (host) is query b's filter, -1 for
  * every live row; the batch is grouped by filter, one pass per distinct one
  * (-1: mhnsw_search in MHNSW_MODE_EXACT), each query's results at its own
  * position.  mhnsw_search_filtered_exact_device: one filter (or -1) for the
  * whole batch, enqueued on `stream` with the handle's workspace like
  * mhnsw_search_device; a caller with a mixed batch groups it.  Errors:
- * MHNSW_EUNSUPPORTED "exact mode supports k <= 256", MHNSW_EINVAL "unknown
+ * MHNSW_EUNSUPPORTED "exact mode supports k <= 256" (with "exact_wide":
+ * "exact mode supports k <= 4096"), MHNSW_EINVAL "unknown
  * filter %d".  mhnsw_last_kernel_ms covers the last pass, compaction through
  * re-rank; the read-only options last_fx_compact_ns, last_fx_gather_ns and (of
  * the first chunk of queries; the exact mode runs a large batch in chunks)
