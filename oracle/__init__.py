@@ -109,6 +109,7 @@ def lib():
         L.og_search_negatives.argtypes = [C.c_void_p, f32p, C.c_int64, C.c_int, f32p, i32p, C.c_int, C.c_float,
                                           C.c_int, C.c_int, C.c_int, i64p, f32p, i32p]
         L.og_export_edge_dist.argtypes = [C.c_void_p, f32p, C.c_int]
+        L.og_import_edge_dist.argtypes = [C.c_void_p, f32p, C.c_int]
         L.og_add_batch.argtypes = [C.c_void_p, i64p, f32p, C.c_int64, C.c_int, i32p, P(BatchCfg), i64p]
         L.og_update.argtypes = [C.c_void_p, i64p, f32p, C.c_int64, C.c_int, P(BatchCfg), u8p, i64p]
         L.og_set_batch_descending.argtypes = [C.c_void_p, C.c_int]
@@ -348,7 +349,9 @@ class Graph:
                                     _p(out, C.c_uint8)))
         return [bool(x) for x in out[:len(keys)]]
 
-    def import_graph(self, keys, vecs, deg, adj, entry, dead=None):
+    def import_graph(self, keys, vecs, deg, adj, entry, dead=None, edge_dist=None):
+        """edge_dist: export_edge_dist()'s array for this graph; a batched build needs it to go on
+        (a commit re-ranks old rows by their stored distances)."""
         keys = np.ascontiguousarray(keys, np.int64)
         vecs = f32(vecs)
         deg = np.ascontiguousarray(deg, np.int32)
@@ -361,6 +364,10 @@ class Graph:
                                     _p(keys, C.c_int64), _p(vecs, C.c_float), _p(deg, C.c_int32),
                                     _p(adj, C.c_int32), _p(entry, C.c_int32),
                                     None if dd is None else _p(dd, C.c_uint8)))
+        if edge_dist is not None:
+            ed = f32(edge_dist)
+            assert ed.shape == adj.shape
+            self._check(lib().og_import_edge_dist(self._h, _p(ed, C.c_float), cap))
 
     def stats(self):
         o = np.zeros(4, np.int64)

@@ -1574,6 +1574,22 @@ int og_export_edge_dist(og_graph *g, float *adjd, int cap) {
     return OG_OK;
 }
 
+/* og_export_edge_dist's counterpart: after og_import, which leaves the stored
+ * distances unset, an imported batched graph can go on being built (a commit
+ * re-ranks old rows by them). */
+int og_import_edge_dist(og_graph *g, const float *adjd, int cap) {
+    for (int l = 0; l < g->nlayers; ++l) {
+        og_layer *L = &g->layers[l];
+        for (int64_t i = 0; i < g->n; ++i) {
+            const int d = L->deg[i];
+            if (d > cap || d > g->acap) return set_err(g, OG_EINVAL, "import cap too small");
+            const float *in = adjd + ((size_t)l * g->n + i) * cap;
+            for (int j = 0; j < g->acap; ++j) L->adjd[(size_t)i * g->acap + j] = (j < d) ? in[j] : 0.f;
+        }
+    }
+    return OG_OK;
+}
+
 /* ------------------------------------------------------------------------ */
 /* batched insert, link pass, update (the engine's own algorithms)           */
 /* ------------------------------------------------------------------------ */
@@ -1585,7 +1601,14 @@ int og_export_edge_dist(og_graph *g, float *adjd, int cap) {
  * whatever their arrival order.  The engine drops a proposal when a row
  * receives more than inc_cap of them in one commit -- which ones depends on
  * arrival order there -- so the restatement equals the engine only where
- * counter OG_C_DROPPED stays 0. */
+ * counter OG_C_DROPPED stays 0.  Where it does not, the restatement keeps the
+ * first inc_cap in the order it takes the rows, which is one valid arrival
+ * order and the descending run another (two different graphs).  What holds for
+ * any order: a row past the cap is the commit of the old row and some inc_cap
+ * of its proposals, every other row equals the run with room for all of them,
+ * OG_C_DROPPED is the engine's count exactly, and the next batch is exact
+ * again (tests/overflow_ref.py decides that set; og_import_edge_dist continues
+ * from an engine-built graph). */
 
 int og_set_batch_descending(og_graph *g, int on) {
     g->batch_desc = on != 0;

@@ -154,6 +154,10 @@ int og_import(og_graph *g, int64_t N, int dim, int L, int cap, const int64_t *ke
  * carried to the other end by the proposal.  Rows written by the compat insert
  * (og_add) carry none. */
 int og_export_edge_dist(og_graph *g, float *adjd, int cap);
+/* The counterpart, after og_import (which leaves them unset): a commit re-ranks
+ * old rows by their stored distances, so an imported graph needs them to
+ * continue a batched build. */
+int og_import_edge_dist(og_graph *g, const float *adjd, int cap);
 
 /* ---- the engine's batched insert, link pass and update, restated ----------
  * Options as the engine's (include/mhnsw.h): efc = ef_construction (0: EfSearch),
