@@ -1483,6 +1483,9 @@ int mhnsw_set_option(mhnsw_index* h, const char* name, int64_t v) {
     } else if (n == "vis_compact") {
         if (v != 0 && v != 1) return fail(h, MHNSW_EINVAL, "vis_compact must be 0 or 1");
         h->vis_compact = (int)v;
+    } else if (n == "filter_wide") {
+        if (v < 0 || v > 1) return fail(h, MHNSW_EINVAL, "filter_wide must be 0 or 1");
+        h->filter_wide = (int)v;
     } else if (n == "filter_route") {
         if (v < 1 || v > 2048) return fail(h, MHNSW_EINVAL, "filter_route must be in [1, 2048]");
         h->filter_route = (int)v;
@@ -1572,6 +1575,7 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
     else if (n == "fuse_descent") *v = h->fuse_descent;
     else if (n == "vis_compact") *v = h->vis_compact;
     else if (n == "filter_route") *v = h->filter_route;
+    else if (n == "filter_wide") *v = h->filter_wide;
     else if (n == "time_build") *v = h->time_build;
     else if (n == "max_rows") *v = h->max_rows;
     else if (n == "strkey_relabels") *v = h->relabels;

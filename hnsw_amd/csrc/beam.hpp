@@ -4,8 +4,9 @@
 // modes x 10 configurations compile in parallel).  One body, beam_query, runs
 // a query over either list: BList<R> in registers (k_search_beam,
 // k_search_beam_mw), or past them (max(ef, k) > 512) LList in LDS
-// (k_search_beam_lds).  The filtered search (k_search_beam_filt) is the same
-// body with the RowFilter policy over the LDS list.
+// (k_search_beam_lds).  The filtered search (k_search_beam_filt, and past 128
+// results k_search_beam_filt_wide) is the same body with the RowFilter /
+// RowFilterWide policy over the LDS list.
 #pragma once
 #include <type_traits>
 
@@ -24,6 +25,8 @@ template <int L, int V, int XW>
 int launch_beam_lds_cfg(const SearchArgs& a, hipStream_t s);
 template <int L, int V>
 int launch_beam_filt_cfg(const SearchArgs& a, const FilterArgs& f, hipStream_t s);
+template <int L, int V>
+int launch_beam_filt_wide_cfg(const SearchArgs& a, const FilterArgs& f, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // batched search: one wave per query
@@ -61,6 +64,13 @@ __host__ __device__ inline BeamLds beam_lds(const SearchArgs& a) {
     }
 }
 constexpr size_t BEAM_LDS_MAX_BYTES = 64 * 1024;  // a workgroup's LDS without an opt-in attribute
+// The wide filtered launch (k_search_beam_filt_wide): the LDS tier's layout for
+// the route list, then the result list R at `list`, E = f.ef entries rounded up
+// to 64 (distances, then ids; R shares the route list's candidate buffer).
+__host__ __device__ inline BeamLds beam_lds_filt_wide(const SearchArgs& a, int E) {
+    const int at = beam_lds<LList>(a).words;  // (a multiple of 4)
+    return {at, at + 2 * ll_cap(E)};
+}
 
 // 0, or why no layer-0 launch of the given tier (lds: the LDS list, else the
 // register lists) runs these arguments: -4 past the capacity of the tier's
@@ -466,6 +476,44 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_search_be
     beam_stats(a, st);
 }
 
+// ---------------------------------------------------------------------------
+// filtered search past 128 results (128 < max(ef, k) <= LL_MAX_EF; DESIGN.md
+// "Filtered search past 128 results"): the same wave with the RowFilterWide
+// policy, R in LDS behind the route list and merged once per step.  A kernel of
+// its own, so that k_search_beam_filt stays what it was.
+// ---------------------------------------------------------------------------
+template <class C, int G, bool SCREEN>
+__global__ __attribute__((amdgpu_flat_work_group_size(64, 64))) void k_search_beam_filt_wide(SearchArgs a, FilterArgs f) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const int64_t b = blockIdx.x;
+    if (b >= a.B) return;
+    RowFilterWide flt;
+    flt.E = f.ef;
+    flt.bits = nullptr;
+    const int32_t fi = uni(f.filter_of[b]);
+    if (fi != -1) {  // (-1: every live row)
+        const uint32_t* bits = fi >= 0 && fi < f.nslots ? f.filters[fi] : nullptr;
+        if (!bits) {  // names no filter: no results, reported like the other device errors
+            if (lane_id() == 0) atomicOr(a.err, 8);
+            beam_pad_out(a, b, 0);
+            return;
+        }
+        flt.bits = bits;
+    }
+    uint32_t* rmem = smem + beam_lds_filt_wide(a, f.ef).list;
+    flt.R.cap = ll_cap(f.ef);
+    flt.R.cb = nullptr;
+    flt.R.d = reinterpret_cast<float*>(rmem);
+    flt.R.i = rmem + flt.R.cap;
+    flt.R.n = flt.R.nx = 0;
+    QReg<C> q;
+    load_query(q, a.q + (size_t)b * C::PITCH);
+    const float qn = query_norm(q);
+    WaveStats st;
+    beam_query_f<C, LList, G, SCREEN, 1>(a, b, q, qn, smem, st, WaveBatch(), flt);
+    beam_stats(a, st);
+}
+
 // f(std::true_type / std::false_type): the kernels with and without the fp16 screen
 template <class F>
 int beam_with_screen(const SearchArgs& a, F&& f) {
@@ -522,6 +570,20 @@ int launch_beam_filt_cfg(const SearchArgs& a, const FilterArgs& f, hipStream_t s
     const int lds = beam_lds<LList>(a).words;
     return beam_with_screen(a, [&](auto screen) {
         hipLaunchKernelGGL((k_search_beam_filt<Cfg<L, V>, cfg_group<L, V>(), decltype(screen)::value>),
+                           dim3((unsigned)a.B), dim3(64), (size_t)4 * (size_t)lds, s, a, f);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    });
+}
+
+// the wide filtered launch: beam_limits over the route width, then R's part of the LDS
+template <int L, int V>
+int launch_beam_filt_wide_cfg(const SearchArgs& a, const FilterArgs& f, hipStream_t s) {
+    if (f.ef <= 128 || f.ef > LL_MAX_EF || a.k > f.ef || a.ef < f.ef) return -4;
+    if (const int rc = beam_limits(a, true)) return rc;
+    const int lds = beam_lds_filt_wide(a, f.ef).words;
+    if ((size_t)4 * (size_t)lds > BEAM_LDS_MAX_BYTES) return -2;
+    return beam_with_screen(a, [&](auto screen) {
+        hipLaunchKernelGGL((k_search_beam_filt_wide<Cfg<L, V>, cfg_group<L, V>(), decltype(screen)::value>),
                            dim3((unsigned)a.B), dim3(64), (size_t)4 * (size_t)lds, s, a, f);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     });

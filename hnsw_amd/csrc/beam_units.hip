@@ -8,6 +8,8 @@
 //   beam_w1a/b .. w4a/b    k_search_beam_lds (the LDS-resident list, max(ef, k)
 //                          past the register lists), XW 1 / 2 / 4, groups A B / C D
 //   beam_fa, beam_fb       k_search_beam_filt (the filtered search), groups A B / C D
+//   beam_fwa, beam_fwb     k_search_beam_filt_wide (the filtered search past 128
+//                          results), groups A B / C D
 //   beam_desc              k_beam_descend (the ordered path's descent pre-pass),
 //                          every configuration
 #include "beam.hpp"
@@ -23,6 +25,7 @@
 #define LDS2_(L, V, G) template int launch_beam_lds_cfg<L, V, 2>(const SearchArgs&, hipStream_t);
 #define LDS4_(L, V, G) template int launch_beam_lds_cfg<L, V, 4>(const SearchArgs&, hipStream_t);
 #define FILT_(L, V, G) template int launch_beam_filt_cfg<L, V>(const SearchArgs&, const FilterArgs&, hipStream_t);
+#define FILTW_(L, V, G) template int launch_beam_filt_wide_cfg<L, V>(const SearchArgs&, const FilterArgs&, hipStream_t);
 #define DESC_(L, V, G) template int launch_beam_descend_cfg<L, V>(const SearchArgs&, hipStream_t);
 
 #define U_beam_a MH_CFGS_A(REG1_)
@@ -41,6 +44,8 @@
 #define U_beam_w4b MH_CFGS_C(LDS4_) MH_CFGS_D(LDS4_)
 #define U_beam_fa MH_CFGS_A(FILT_) MH_CFGS_B(FILT_)
 #define U_beam_fb MH_CFGS_C(FILT_) MH_CFGS_D(FILT_)
+#define U_beam_fwa MH_CFGS_A(FILTW_) MH_CFGS_B(FILTW_)
+#define U_beam_fwb MH_CFGS_C(FILTW_) MH_CFGS_D(FILTW_)
 #define U_beam_desc MH_FOR_EACH_CFG(DESC_)
 
 #define MH_UNIT_CAT2(a, b) a##b

@@ -549,6 +549,8 @@ __device__ __forceinline__ float bl_picked_dist(const LList& L) {
 // An infinite distance, two equal candidate distances, a candidate equal to a
 // listed distance and a candidate past every listed entry (lb >= ef) send the
 // buffer through bl_insert, one candidate at a time.
+// (ll_merge_ranked, below, restates the search, the shift and the placement for
+// the wide filtered kernel: a fix to either belongs in both.)
 __device__ __forceinline__ void bl_merge(LList& L, int ef, int k, float*) {
     const int lane = lane_id();
     const float INF = __int_as_float(0x7f800000);
@@ -722,6 +724,135 @@ struct RowFilter {
 };
 
 // ---------------------------------------------------------------------------
+// RowFilterWide: RowFilter's semantics with R in LDS, 128 < E <= LL_MAX_EF
+// (k_search_beam_filt_wide; DESIGN.md "Filtered search past 128 results").
+// R is a second LList behind the route list; it has no candidate buffer of its
+// own.  A step buffers what it offers in L's buffer, as every MERGE step does,
+// and notes in `am` which of the buffered candidates are allowed; at the end of
+// the step flt_merge ranks the buffer once and merges it into L, and its allowed
+// sub-sequence into R.  R's worst entry as the next step's head needs it
+// (+inf / EMPTY_ID until R is full) stays in wd / wi, refreshed after a merge
+// that touched R: a step that offers nothing allowed reads nothing of R.
+// ---------------------------------------------------------------------------
+struct RowFilterWide {
+    static constexpr bool on = true;
+    const uint32_t* bits;   // row id -> bit, 32 rows a word (nullptr: every live row)
+    int E;                  // R's capacity: 128 < max(ef, k) <= LL_MAX_EF
+    LList R;                // (d, i, cap placed by the kernel; cb unused)
+    float wd;               // R[E - 1], uniform
+    uint32_t wi;
+    unsigned long long am;  // bit j: the step's j-th buffered candidate is allowed
+    __device__ __forceinline__ bool allowed(const GraphDev& g, uint32_t id) const {
+        const bool bit = bits ? ((bits[id >> 5] >> (id & 31)) & 1u) != 0 : true;
+        return bit && !is_dead(g, id);
+    }
+    __device__ __forceinline__ void refresh() { bl_at(R, E - 1, wd, wi); }
+};
+template <class Flt>
+constexpr bool flt_wide = false;
+template <>
+inline constexpr bool flt_wide<RowFilterWide> = true;
+
+// The candidates held by the lanes `in` (m >= 1 of them; bd / bi their distance
+// and id; distinct finite distances, rk a candidate's rank among the m) into the
+// LDS list: bl_merge(LList)'s lower bound over L.d[0, ef], its in-place shift in
+// 64-entry chunks from the tail down and its placement, for a candidate set
+// that is any subset of the wave's lanes, not lanes [0, k).  As there, a
+// candidate equal to a listed distance or past every listed entry sends the
+// set through bl_insert.  (bl_merge(LList) keeps its own copy of these steps:
+// the LDS kernels and the narrow filtered kernel are built from it as they were.)
+__device__ __forceinline__ void ll_merge_ranked(LList& L, int ef, bool in, int m, int rk, float bd, uint32_t bi) {
+    const int lane = lane_id();
+    int lb = 0;  // the list entries (of the first ef) below the lane's candidate
+    if (in) {
+        // (the steps add up to 2 LL_MAX_EF - 1 >= ef, so lb can reach ef)
+#pragma unroll
+        for (int step = LL_MAX_EF; step >= 1; step >>= 1) {
+            const int t = lb + step - 1;
+            if (t < ef && L.d[t] < bd) lb += step;
+        }
+    }
+    const unsigned long long im = __ballot(in);
+    if (__ballot(in && (lb >= ef || L.d[lb < ef ? lb : 0] == bd)) != 0) {
+        for (unsigned long long w = im; w; w &= w - 1) {
+            const int j = __ffsll((long long)w) - 1;
+            bl_insert(L, ef, rl_f(bd, j), rl_u(bi, j));
+        }
+        return;
+    }
+    const int n = L.n;
+    const int minlb = rl_i(lb, __ffsll((long long)__ballot(in && rk == 0)) - 1);
+    const int maxlb = rl_i(lb, __ffsll((long long)__ballot(in && rk == m - 1)) - 1);
+    for (int c = (n - 1) >> 6; c >= (minlb >> 6); --c) {
+        const int idx = c * 64 + lane;
+        const bool mv = idx >= minlb && idx < n;
+        const float ed = mv ? L.d[idx] : 0.f;
+        const uint32_t ei = mv ? L.i[idx] : 0u;
+        int sh = m;  // the candidates placed at or before entry idx
+        if (c * 64 < maxlb) {
+            sh = 0;
+            for (unsigned long long w = im; w; w &= w - 1) sh += idx >= rl_i(lb, __ffsll((long long)w) - 1) ? 1 : 0;
+        }
+        wave_sync();  // (the chunk is read whole before any of it is overwritten)
+        if (mv && idx + sh < ef) {
+            L.d[idx + sh] = ed;
+            L.i[idx + sh] = ei;
+        }
+        wave_sync();
+    }
+    const int pos = rk + lb;
+    if (in && pos < ef) {
+        L.d[pos] = bd;
+        L.i[pos] = bi;
+    }
+    wave_sync();
+    const int up = __popcll(__ballot(in && lb <= L.nx));
+    L.nx = min(L.nx + up, minlb);
+    L.n = min(n + m, ef);
+}
+
+// The end of a RowFilterWide step: the k <= 64 candidates of L.cb (arrival
+// order; f.am marks the allowed ones) into the route list L and the allowed
+// ones into f.R.  One pass ranks every candidate among all of them and, from
+// the same compares, among the allowed ones -- the allowed candidates are a
+// sub-sequence of the buffer's (distance, id) order -- then each list takes its
+// set through ll_merge_ranked.  An infinite distance or two equal candidate
+// distances send both sets through bl_insert, as bl_merge does.
+__device__ __forceinline__ void flt_merge(LList& L, int ef, RowFilterWide& f, int k) {
+    const int lane = lane_id();
+    const float INF = __int_as_float(0x7f800000);
+    const unsigned long long am = f.am;
+    wave_sync();  // (the buffer was written by lane 0)
+    const float bd = lane < k ? L.cb[lane] : INF;
+    const uint32_t bi = lane < k ? reinterpret_cast<const uint32_t*>(L.cb)[64 + lane] : EMPTY_ID;
+    bool slow = __ballot(lane < k && !(bd < INF)) != 0;
+    int rk = 0, rka = 0;  // lane j < k: the candidates, and the allowed candidates, below candidate j
+    if (!slow) {
+        int eq = 0;
+        for (int j = 0; j < k; ++j) {
+            const float dj = rl_f(bd, j);
+            const int lt = dj < bd ? 1 : 0;
+            rk += lt;
+            rka += (int)((am >> j) & 1ull) & lt;
+            eq += dj == bd ? 1 : 0;
+        }
+        slow = __ballot(lane < k && eq > 1) != 0;
+    }
+    if (slow) {
+        for (int j = 0; j < k; ++j) {
+            const float d = rl_f(bd, j);
+            const uint32_t u = rl_u(bi, j);
+            bl_insert(L, ef, d, u);
+            if ((am >> j) & 1ull) bl_insert(f.R, f.E, d, u);
+        }
+    } else {
+        ll_merge_ranked(L, ef, lane < k, k, rk, bd, bi);
+        if (am) ll_merge_ranked(f.R, f.E, ((am >> lane) & 1ull) != 0, __popcll(am), rka, bd, bi);
+    }
+    if (am) f.refresh();
+}
+
+// ---------------------------------------------------------------------------
 // beam: sorted list of <= ef entries; stop when every entry is expanded
 // ---------------------------------------------------------------------------
 // XW: entries expanded per step.  1 is the standard best-first search (the
@@ -741,8 +872,8 @@ struct RowFilter {
 // through bl_merge once per step, with `mrg` (BL_MERGE_WORDS of LDS) as its
 // scratch.
 // LT: the list, BList<R> (registers) or LList (LDS).
-// Flt: the filter policy (NoFilter; RowFilter with the LDS list, XW 1 and MERGE,
-// where a step is one batch, so "before the step" is "before the batch").
+// Flt: the filter policy (NoFilter; RowFilter / RowFilterWide with the LDS list,
+// XW 1 and MERGE, where a step is one batch, so "before the step" is "before the batch").
 template <class C, class LT, int G, bool COH, bool SCREEN, int XW, bool MERGE, class BEv, class Flt>
 __device__ __forceinline__ void beam_layer_l(const GraphDev& g, int layer, uint32_t entry, int ef, const QReg<C>& q,
                                              float qn, LT& L, uint32_t* vis, int vsize, WaveStats& st, const BEv& bev,
@@ -751,6 +882,7 @@ __device__ __forceinline__ void beam_layer_l(const GraphDev& g, int layer, uint3
     const int lane = lane_id();
     bl_init(L);
     if constexpr (Flt::on) bl_init(flt.R);
+    if constexpr (flt_wide<Flt>) flt.refresh();
     if (entry == EMPTY_ID) return;
     vis_any_clear(vis, vsize);
     wave_sync();  // (the list and the visited set belong to this wave alone)
@@ -762,6 +894,7 @@ __device__ __forceinline__ void beam_layer_l(const GraphDev& g, int layer, uint3
             bl_insert(L, ef, d, u);
             if (ok) bl_insert(flt.R, flt.E, d, u);
         });
+        if constexpr (flt_wide<Flt>) flt.refresh();
     } else {
         eval_list<C, G>(g, q, qn, entry, 1, g.metric, [&](float d, uint32_t u) { bl_insert(L, ef, d, u); });
     }
@@ -794,8 +927,14 @@ __device__ __forceinline__ void beam_layer_l(const GraphDev& g, int layer, uint3
         if (cur[0] == EMPTY_ID) break;
         float rwd = __int_as_float(0x7f800000);  // Flt: R's worst entry before the step
         uint32_t rwi = EMPTY_ID;
-        if constexpr (Flt::on) {
+        if constexpr (flt_wide<Flt>) {  // (kept across the steps: no LDS read here)
+            rwd = flt.wd;
+            rwi = flt.wi;
+            flt.am = 0;
+        } else if constexpr (Flt::on) {
             bl_at(flt.R, flt.E - 1, rwd, rwi);
+        }
+        if constexpr (Flt::on) {
             // R is full and its worst entry precedes the best unexpanded one:
             // nothing left can improve the results
             if (rwi != EMPTY_ID && lt_di(rwd, rwi, bl_picked_dist(L), cur[0] & ID_MASK)) break;
@@ -882,11 +1021,27 @@ __device__ __forceinline__ void beam_layer_l(const GraphDev& g, int layer, uint3
             st.E += cnt;
             if constexpr (MERGE) {
                 {
-                    if (bk + cnt > 64) {  // (a batch adds at most cnt)
+                    // (a batch adds at most cnt; RowFilterWide: XW 1, the step's one batch fits)
+                    if (!flt_wide<Flt> && bk + cnt > 64) {
                         bl_merge(L, ef, bk, mrg);
                         bk = 0;
                     }
                     float* cb = bl_cbuf(L, mrg);
+                    if constexpr (flt_wide<Flt>) {
+                        // RowFilter's offer, below; the allowed ones are marked, not inserted
+                        auto sink = [&](float d, uint32_t u) {
+                            if (lt_di(d, u, wd, wi & ID_MASK) && lt_di(d, u, rwd, rwi)) {
+                                if (lane == 0) {
+                                    cb[bk] = d;
+                                    reinterpret_cast<uint32_t*>(cb)[64 + bk] = u;
+                                }
+                                if (__ballot(lane < cnt && cid == u && cok) != 0) flt.am |= 1ull << bk;
+                                ++bk;
+                            }
+                        };
+                        st.F += bev.template score<C, G, SCREEN>(g, q, qn, cid, cnt, sd, screen, margin, sink, st.S);
+                        continue;
+                    }
                     if constexpr (Flt::on) {
                         // offered: below both worst entries as saved before the step (R's
                         // live bound falls inside the step; the saved one decides)
@@ -934,7 +1089,9 @@ __device__ __forceinline__ void beam_layer_l(const GraphDev& g, int layer, uint3
             st.F += bev.template score<C, G, SCREEN>(g, q, qn, cid, cnt, wd, screen, margin, sink, st.S);
 #endif
         }
-        if constexpr (MERGE) {
+        if constexpr (flt_wide<Flt>) {
+            if (bk > 0) flt_merge(L, ef, flt, bk);
+        } else if constexpr (MERGE) {
             if (bk > 0) bl_merge(L, ef, bk, mrg);
         }
         if (vcount > MH_VIS_FULL(vis_any_cap(vsize))) {  // reset: results unchanged

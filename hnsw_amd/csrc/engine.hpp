@@ -113,7 +113,7 @@ struct SearchArgs {
 struct FilterArgs {
     const uint32_t* const* filters;  // [nslots] a filter's bitmap, row id -> bit (nullptr: no such filter)
     int nslots;
-    int ef;                          // max(ef, k) <= 128
+    int ef;                          // max(ef, k): <= 128 k_search_beam_filt, <= 2048 k_search_beam_filt_wide
     const int32_t* filter_of;        // [B] query b's filter (-1: every live row)
 };
 
@@ -161,6 +161,9 @@ int launch_sweep(const float* q, const float* X, int64_t n, int pitch, int lpr, 
 int launch_sweep_raw(const float* q, const float* X, int64_t n, int dim, int metric, float* out, hipStream_t s);
 int launch_search_beam(const SearchArgs& a, int lpr, int vpl, hipStream_t s);
 int launch_search_beam_filtered(const SearchArgs& a, const FilterArgs& f, int lpr, int vpl, hipStream_t s);
+// the 32-bit visited-set entries that fit a workgroup's LDS next to a route list of W and a
+// result list of E > 128 entries (the wide filtered launch)
+int filtered_wide_vis_room(int W, int E);
 // ordered path: the descent pre-pass (writes a.ep0 / a.okey / a.oidx, adds its
 // counters to a.stats), then the sort of the keys into the permutation (order.hip)
 int launch_beam_descend(const SearchArgs& a, int lpr, int vpl, hipStream_t s);

@@ -239,6 +239,7 @@ struct mhnsw_index {
     const uint32_t** d_filters = nullptr;  // [MHNSW_MAX_FILTERS] device table of the bitmaps (nullptr: none)
     bool filters_dirty = false;            // the table is to be uploaded
     int filter_route = 1024;               // route width of a filtered search that names none
+    int filter_wide = 0;                   // 1: the filtered walk accepts max(ef, k) <= 2048 (R in LDS past 128)
     DevBuf<int32_t> fof;                   // a host-pointer filtered search's filter_of
     // filtered exact search (rowset.hip): the allowed rows of the call's filter as a row set --
     // bitmap words, per-block counts, row mask of the fallback, the ascending ids, their rows

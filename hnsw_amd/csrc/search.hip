@@ -19,6 +19,7 @@ namespace mh {
     extern template int launch_beam_lds_cfg<L, V, 4>(const SearchArgs&, hipStream_t); \
     extern template int launch_beam_descend_cfg<L, V>(const SearchArgs&, hipStream_t); \
     extern template int launch_beam_filt_cfg<L, V>(const SearchArgs&, const FilterArgs&, hipStream_t); \
+    extern template int launch_beam_filt_wide_cfg<L, V>(const SearchArgs&, const FilterArgs&, hipStream_t); \
     extern template int launch_compat_cfg<L, V>(const SearchArgs&, hipStream_t);     \
     extern template int launch_negatives_cfg<L, V>(const NegArgs&, hipStream_t);
 MH_FOR_EACH_CFG(X_)
@@ -445,7 +446,13 @@ int launch_search_beam(const SearchArgs& a, int lpr, int vpl, hipStream_t s) {
 
 int launch_search_beam_filtered(const SearchArgs& a, const FilterArgs& f, int lpr, int vpl, hipStream_t s) {
     if (a.B <= 0) return 0;
-    return with_cfg(lpr, vpl, [&](auto c) { return launch_beam_filt_cfg<c.L, c.V>(a, f, s); });
+    // the result list's tier: registers up to 128 entries, LDS past them
+    if (f.ef <= 128) return with_cfg(lpr, vpl, [&](auto c) { return launch_beam_filt_cfg<c.L, c.V>(a, f, s); });
+    return with_cfg(lpr, vpl, [&](auto c) { return launch_beam_filt_wide_cfg<c.L, c.V>(a, f, s); });
+}
+
+int filtered_wide_vis_room(int W, int E) {
+    return (int)(BEAM_LDS_MAX_BYTES / 4) - ll_words(W) - 2 * ll_cap(E) - 4;
 }
 
 // The pre-pass's counters: k_beam_descend leaves each query's E, X, S and F in

@@ -692,10 +692,20 @@ static int search_plain(mhnsw_index* h, SearchCall& c, int mode, int ef, const i
     return r ? r : finish(h, c);
 }
 
+// The filtered walk's limit on its result width E = max(ef, k): the register list's 128, or with
+// the option "filter_wide" the LDS list's 2048 (LL_MAX_EF)
+static int filtered_width_limit(mhnsw_index* h, int E) {
+    if (h->filter_wide && E > 2048) return fail(h, MHNSW_EUNSUPPORTED, "filtered search supports max(ef,k) <= 2048");
+    if (!h->filter_wide && E > 128) return fail(h, MHNSW_EUNSUPPORTED, "filtered search supports max(ef,k) <= 128");
+    return 0;
+}
+
 // The filtered walk's launch on c.s, for the filtered search and the filtered range search's
 // beam mode: lists of the E best allowed rows per query (to c's outputs, staged here) through
-// an LDS route list of W entries.  filter_of: a host array of checked ids (it is uploaded), or
-// for a device call the device's.  timed: the walk's event pair is recorded.
+// an LDS route list of W entries (E <= 128: R in registers; wider, option "filter_wide": R in
+// LDS behind the route list, launch_search_beam_filtered picks the kernel).  filter_of: a host
+// array of checked ids (it is uploaded), or for a device call the device's.  timed: the walk's
+// event pair is recorded.
 static int filtered_walk(mhnsw_index* h, SearchCall& c, int E, int W, const int32_t* filter_of, bool timed) {
     int r;
     // a bitmap that has to grow with the rows moves: nothing enqueued may read it
@@ -714,8 +724,15 @@ static int filtered_walk(mhnsw_index* h, SearchCall& c, int E, int W, const int3
     if ((r = walk_args(h, c, top, (uint32_t)h->layers[top].entry, W, true, a))) return r;
     a.mw_max_b = 0;
     a.expand = 1;
+    // past 128 results the result list takes LDS too: an automatically sized 32-bit set gives way
+    // to it (never below the set the narrow lists search with; the results do not depend on it)
+    if (E > 128 && !a.vis16 && h->vis_entries <= 0)
+        a.vis_n = std::max(beam_vis_entries(h), std::min(a.vis_n, filtered_wide_vis_room(W, E)));
     if (timed) HIPCHK(h, hipEventRecord(h->ev0, c.s));
     const int lr = launch_search_beam_filtered(a, f, h->lpr, h->vpl, c.s);
+    if (lr == -2 && E > 128)
+        return fail(h, MHNSW_EUNSUPPORTED, "filtered search LDS budget exceeded (route=%d, results=%d, vis_entries=%d)", W,
+                    E, a.vis_n);
     if (lr == -2)
         return fail(h, MHNSW_EUNSUPPORTED, "filtered search LDS budget exceeded (route=%d, vis_entries=%d)", W, a.vis_n);
     LCHK(h, lr);
@@ -730,7 +747,7 @@ static int search_filtered(mhnsw_index* h, SearchCall& c, int ef, int route, con
     if (r || (r = check_args(h, c, MHNSW_MODE_BEAM))) return r;
     if (ef <= 0) ef = h->ef;
     const int E = std::max(ef, c.k);
-    if (E > 128) return fail(h, MHNSW_EUNSUPPORTED, "filtered search supports max(ef,k) <= 128");
+    if ((r = filtered_width_limit(h, E))) return r;
     if (route <= 0) route = h->filter_route;
     const int W = std::max(route, E);
     if (W > 2048) return fail(h, MHNSW_EUNSUPPORTED, "filtered search supports route <= 2048");  // (LL_MAX_EF)
@@ -1217,7 +1234,7 @@ static int range_search(mhnsw_index* h, SearchCall& c, int mode, int ef, const R
     const bool walk = rows.walk && mode == MHNSW_MODE_BEAM;
     int W = 0;
     if (walk) {  // the filtered walk's limits, in its words
-        if (std::max(ef, 1) > 128) return fail(h, MHNSW_EUNSUPPORTED, "filtered search supports max(ef,k) <= 128");
+        if ((r = filtered_width_limit(h, std::max(ef, 1)))) return r;
         W = std::max(rows.route > 0 ? rows.route : h->filter_route, std::max(ef, 1));
         if (W > 2048) return fail(h, MHNSW_EUNSUPPORTED, "filtered search supports route <= 2048");  // (LL_MAX_EF)
     }

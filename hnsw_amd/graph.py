@@ -638,7 +638,8 @@ class Graph:
         float32[B,k], n int32[B]).  filters: one Filter, or one per query (None:
         every live row).  MODE_BEAM routes through a list of `route` entries
         (0: option filter_route) and keeps the max(ef, k) <= 128 best allowed
-        rows; a route too narrow for the filter returns fewer than k.
+        rows (<= 2048 with the option filter_wide=1, Graph(..., filter_wide=1));
+        a route too narrow for the filter returns fewer than k.
         MODE_EXACT is the brute force over the allowed rows only (one pass per
         distinct filter; ef and route are ignored): the exact k nearest, which
         pays at selective filters (DESIGN.md "Filtered exact search")."""
@@ -707,8 +708,9 @@ class Graph:
         filters: one Filter, or one per query (None: every live row) -- only
         allowed rows are hits.  MODE_EXACT then works over the allowed rows only
         (one pass per distinct filter); MODE_BEAM is the filtered walk at k = ef
-        <= 128 through a list of `route` entries (0: option filter_route), cut
-        by the radius (DESIGN.md "Filtered range search")."""
+        <= 128 (<= 2048 with the option filter_wide=1) through a list of `route`
+        entries (0: option filter_route), cut by the radius (DESIGN.md
+        "Filtered range search")."""
         q, rad = self._range_io(queries, radius, mode)
         B, d = q.shape
         fo = None if filters is None else np.ascontiguousarray(self._filter_ids(filters, B))

@@ -391,7 +391,8 @@ class Graph {  // graph.go:305-332
     Filter MakeFilter(const std::vector<K>& keys) { return Filter(*this, keys); }
 
     // the k nearest rows of `filter` (nullptr: every live row); ef <= 0:
-    // EfSearch, route <= 0: the option filter_route
+    // EfSearch, route <= 0: the option filter_route.  max(ef, k) <= 128, or
+    // <= 2048 after SetOption("filter_wide", 1)
     std::pair<std::vector<Node<K>>, Error> SearchFiltered(const Vector& near, int k, const Filter* filter, int ef = 0,
                                                           int route = 0) {
         return search_filtered(near, k, filter, ef, route, false);
@@ -418,8 +419,9 @@ class Graph {  // graph.go:305-332
     }
     // ... among the rows of `filter` only (mhnsw.h "filtered range search"; nullptr: every live
     // row, the call above).  MHNSW_MODE_EXACT works over the allowed rows alone;
-    // MHNSW_MODE_BEAM is the filtered walk at k = ef <= 128 through a list of `route` entries
-    // (<= 0: the option filter_route), cut by the radius.
+    // MHNSW_MODE_BEAM is the filtered walk at k = ef <= 128 (<= 2048 after
+    // SetOption("filter_wide", 1)) through a list of `route` entries (<= 0: the option
+    // filter_route), cut by the radius.
     std::pair<std::vector<RangeHit>, Error> RangeSearch(const Vector& near, float radius, const Filter* filter,
                                                         int mode = MHNSW_MODE_EXACT, int ef = 0, int route = 0) {
         return range_search(near, radius, filter, true, mode, ef, route);

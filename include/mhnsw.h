@@ -279,7 +279,16 @@ int mhnsw_filter_destroy(mhnsw_index *h, int filter);
  * "filtered search supports max(ef,k) <= 128" / "filtered search supports
  * route <= 2048"; MHNSW_EINVAL for a filter_of entry that names no filter (the
  * *_device call, whose filter_of is a device pointer, reports it through
- * mhnsw_device_status). */
+ * mhnsw_device_status).
+ * Option "filter_wide" = 1 (default 0; "filter_wide must be 0 or 1"): these
+ * calls and the beam mode of the filtered range search accept max(ef, k) <=
+ * 2048 ("filtered search supports max(ef,k) <= 2048").  Up to 128 the call is
+ * the one above, the same launch; past 128 the result list lives in LDS behind
+ * the route list and is merged once per step, with the same results as the
+ * definition above at any width (route is still raised to max(ef, k)).  The
+ * visited set, the route list and the result list share a workgroup's 64 KiB:
+ * an explicit vis_entries that leaves no room fails with MHNSW_EUNSUPPORTED
+ * "filtered search LDS budget exceeded (route=%d, results=%d, vis_entries=%d)". */
 int mhnsw_search_filtered(mhnsw_index *h, const float *queries, int64_t B, int dim, int k, int ef, int route,
                           const int32_t *filter_of, int64_t *out_keys, float *out_dist, int32_t *out_n);
 int mhnsw_search_filtered_device(mhnsw_index *h, const float *d_queries, int64_t B, int dim, int k, int ef, int route,
@@ -391,7 +400,8 @@ int mhnsw_range_search_device(mhnsw_index *h, const float *d_queries, int64_t B,
  * MHNSW_MODE_BEAM returns the hits the filtered walk finds: mhnsw_search_filtered
  * at k = ef through a route list of `route` entries (0: option filter_route),
  * cut by the radius, with that call's limits and messages ("filtered search
- * supports max(ef,k) <= 128", "filtered search supports route <= 2048"); a
+ * supports max(ef,k) <= 128", or with the option "filter_wide" <= 2048;
+ * "filtered search supports route <= 2048"); a
  * count equal to ef means the list was exhausted.  route is ignored in exact mode.
  * mhnsw_range_search_filtered: filter_of[b] (host) is query b's filter, -1 for
  * every live row.  Synchronous; the hits are left for mhnsw_range_results, with
