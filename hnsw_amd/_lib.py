@@ -53,6 +53,12 @@ SIGNATURES = {
     "mhnsw_search_filtered_exact": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, C.c_int, _i32p, _i64p, _f32p, _i32p]),
     "mhnsw_search_filtered_exact_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp,
                                                      _vp]),
+    "mhnsw_lsh_enable": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint64, _f32p, C.c_int]),
+    "mhnsw_lsh_hash": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, _P(C.c_uint32)]),
+    "mhnsw_lsh_codes": (C.c_int, [_vp, _P(C.c_uint32)]),
+    "mhnsw_lsh_projections": (C.c_int, [_vp, _f32p]),
+    "mhnsw_search_lsh": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, C.c_int, _i64p, _f32p, _i32p, _i32p]),
+    "mhnsw_search_lsh_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mhnsw_range_search": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, _f32p, C.c_int, C.c_int, _i64p]),
     "mhnsw_range_results": (C.c_int, [_vp, _i64p, _f32p, C.c_int64]),
     "mhnsw_range_search_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, C.c_int64, _vp, _vp,

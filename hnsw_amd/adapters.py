@@ -124,6 +124,28 @@ class ExactIndex:
         self._g.close()
 
 
+class LSHIndex(ExactIndex):
+    """hybrid/lsh.go LSHIndex[K] on the GPU: an ExactIndex's flat handle with the LSH index
+    enabled (Graph.EnableLSH).  Add of an existing key replaces its vector and moves it to its
+    new buckets.  GetCandidates as a key list is not built: searches return the size of the
+    candidate set instead (search_batch's ncand)."""
+
+    def __init__(self, numTables: int = 4, numBits: int = 8, distance=CosineDistance, projections=None):
+        super().__init__(distance)
+        self._g.EnableLSH(numTables, numBits, projections=projections)
+
+    def Search(self, query, k: int) -> Tuple[list, List[float]]:  # lsh.go:204 -> (keys, distances)
+        if self.Len() == 0:
+            return [], []
+        ks, od, on, _ = self.search_batch(np.asarray(query, np.float32).reshape(1, -1), k)
+        return ks[0], od[0, : on[0]].tolist()
+
+    def search_batch(self, queries, k: int):
+        """-> (keys [B][<=k], distances float32[B, k], n int32[B], ncand int32[B])."""
+        ok, od, on, nc = self._g.search_lsh_arrays(np.asarray(queries, np.float32), k)
+        return [self._g.decode_keys(ok[b, : on[b]]) for b in range(len(on))], od, on, nc
+
+
 class HNSWAdapter:
     """hybrid/adapter.go HNSWAdapter[K]: SearchableIndex over a Graph."""
 

@@ -1072,6 +1072,8 @@ int add_step(mhnsw_index* h, const int64_t* keys, const float* vecs, bool vecs_o
                                     h->stream));
     LCHK(h, launch_norms(h->vecs, n0, n1, h->pitch, h->lpr, h->vpl, h->norms, h->stream));
     if ((r = h16_rows(h, n0, n1))) return r;
+    if (rep >= 0) lsh_note_all(h);  // (a replaced key's rows below n0 hold a new vector)
+    if ((r = lsh_note_rows(h, n0, n1))) return r;
     h->layers_exist = true;
     h->n = n1;
     bool published = !defer_keys;
@@ -1300,6 +1302,7 @@ void mhnsw_destroy(mhnsw_index* h) {
         if (e) (void)hipEventDestroy(e);
     F(h->uids.p);
     F(h->d_repaired);
+    lsh_free(h);
     F(h->an_bits.p);
     F(h->an_q.p);
     F(h->an_ids.p);
@@ -1486,6 +1489,9 @@ int mhnsw_set_option(mhnsw_index* h, const char* name, int64_t v) {
     } else if (n == "filter_wide") {
         if (v < 0 || v > 1) return fail(h, MHNSW_EINVAL, "filter_wide must be 0 or 1");
         h->filter_wide = (int)v;
+    } else if (n == "lsh_worklist_cap") {  // (a small one sends whole launches to the canonical pass: the same codes)
+        if (v < 0 || v > LSH_WORK_MAX) return fail(h, MHNSW_EINVAL, "lsh_worklist_cap must be in [0, %d]", LSH_WORK_MAX);
+        h->lsh_work_cap = (int)v;
     } else if (n == "filter_route") {
         if (v < 1 || v > 2048) return fail(h, MHNSW_EINVAL, "filter_route must be in [1, 2048]");
         h->filter_route = (int)v;
@@ -1645,6 +1651,27 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
             hipMemcpy(st, h->rstat.p, sizeof st, hipMemcpyDeviceToHost) != hipSuccess)
             return MHNSW_EDEVICE;
         *v = (int64_t)st[n == "last_range_candidates" ? 0 : 1];
+    }
+    // LSH index: the configuration (0: not enabled); read-only, from the device (waits for it): the
+    // (row, projection) signs the canonical pass decided since mhnsw_lsh_enable, the candidates of
+    // the last host-pointer LSH search; the device time of the last table rebuild (HIP events)
+    else if (n == "lsh_tables") *v = h->lsh_T;
+    else if (n == "lsh_bits") *v = h->lsh_b;
+    else if (n == "lsh_worklist_cap") *v = h->lsh_work_cap;
+    else if (n == "last_lsh_uncertain" || n == "last_lsh_candidates") {
+        unsigned long long st[2] = {0, 0};
+        if (h->lsh_stat && ((h->scr_valid && hipEventSynchronize(h->scr_ev) != hipSuccess) ||
+                            hipStreamSynchronize(h->stream) != hipSuccess ||
+                            hipMemcpy(st, h->lsh_stat, sizeof st, hipMemcpyDeviceToHost) != hipSuccess))
+            return MHNSW_EDEVICE;
+        *v = (int64_t)st[n == "last_lsh_uncertain" ? 0 : 1];
+    }
+    else if (n == "last_lsh_rebuild_ns") {
+        float ms = 0.f;
+        if (!h->have_lsh_rebuild || hipEventSynchronize(h->lev1) != hipSuccess ||
+            hipEventElapsedTime(&ms, h->lev0, h->lev1) != hipSuccess)
+            return MHNSW_EINVAL;
+        *v = (int64_t)std::llround((double)ms * 1e6);
     }
     else if (n == "exact_wide") *v = h->exact_wide;
     else if (n == "exact_wide_min_k") *v = h->exact_wide_min_k;
@@ -2122,6 +2149,7 @@ int mhnsw_replace(mhnsw_index* h, const int64_t* keys, const float* vecs, int64_
         LCHK(h, launch_h16_rows(h->vecs, h->norms, lo, hi, h->pitch, h->metric, h->h16, h->h16aux, h->h16err,
                                 h->stream));
     h->xsplit_rows = std::min(h->xsplit_rows, lo);
+    if ((r = lsh_note_ids(h, reinterpret_cast<const uint32_t*>(dids), m, h->stream))) return r;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -2241,6 +2269,7 @@ static int update_impl(mhnsw_index* h, const int64_t* keys, const float* vecs, b
             if (h->screen & 1 && h->h16 && h->h16_metric == h->metric)
                 LCHK(h, launch_h16_rows_ids(h->vecs, h->norms, d_ids + c0, cnt, h->pitch, h->metric, h->h16,
                                             h->h16aux, h->h16err, s));
+            if ((r = lsh_note_ids(h, d_ids + c0, cnt, s))) return r;
             // (planes converted so far, in a buffer of the current capacity: rows past xsplit_rows are
             // written to the values the next exact search gives them anyway; an unconverted or
             // outgrown buffer is rebuilt by that search)
@@ -2573,6 +2602,7 @@ int mhnsw_compact(mhnsw_index* h, int64_t* out_removed) {
     // next exact search (its per-row filter constants are rebuilt by every search); the
     // screening copy moved with the rows, and its error maximum over a superset stays valid
     h->xsplit_rows = 0;
+    lsh_note_all(h);  // the ids moved: every row is hashed again by the next LSH search
     if ((r = sync_layer_entries(h))) return r;
     HIPCHK(h, hipStreamSynchronize(s));
     if (out_removed) *out_removed = n0 - live;

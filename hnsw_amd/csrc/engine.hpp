@@ -493,6 +493,53 @@ int launch_range_place(const int64_t* src_keys, const float* src_dist, const int
 int launch_range_beam(const int64_t* bk, const float* bd, const int32_t* bn, int ef, const float* radius, int64_t B,
                       int32_t* cnt, int64_t* lims, int64_t cap, int64_t* keys, float* dist, hipStream_t s);
 
+// ---- LSH index (lsh.hip): sign codes of random projections, bucket tables, bucket search ----
+constexpr int LSH_MAX_P = 256;      // projections (tables x bits) at most
+constexpr int LSH_PPAD_UNIT = 64;   // the projection matrix holds a multiple of this many rows (zero rows past P)
+// Codes of the rows at positions [r0, r1): position j is row j of X, or row ids[j] (the row list
+// of Replace / Update); the padded queries of a search are X = the query buffer, rows [0, B).
+// Bit i of codes[row * T + t] = (canonical dot of the row and projection t b + i) > 0.
+struct LshHashArgs {
+    const float* X;         // [rows * pitch]
+    const float* xnorm;     // [rows] canonical |x|
+    const uint32_t* ids;    // nullable
+    int64_t r0, r1;
+    int pitch;
+    const float* P;         // [roundup(T b, LSH_PPAD_UNIT) * pitch]
+    const float* pnorm;     // [roundup(T b, LSH_PPAD_UNIT)] canonical |p| (0 for the padding)
+    int T, b;
+    // a sum with |s| <= margin |x| |p| + abs_rel (|x| + |p|) + abs_min is recomputed canonically
+    float margin, abs_rel, abs_min;
+    uint32_t* codes;        // [rows * T]
+    uint2* work;            // [work_cap] {row, projection} of the sums not trusted
+    int work_cap;
+    uint32_t* work_cnt;     // [1] pairs of this launch (past work_cap: the whole launch is redone canonically)
+    unsigned long long* stat;  // [0] += pairs that went to the canonical pass (nullable)
+};
+int launch_lsh_hash(const LshHashArgs& a, int lpr, int vpl, hipStream_t s);
+int lsh_sort_temp_bytes(int64_t n, size_t* bytes);
+// table t of n rows: sorted_code / sorted_id [t * n, (t + 1) * n) = the rows by (code, id); key / val [n] scratch
+int launch_lsh_table(const uint32_t* codes, int T, int t, int bits, int64_t n, uint32_t* key, uint32_t* val,
+                     uint32_t* sorted_code, uint32_t* sorted_id, void* temp, size_t temp_bytes, hipStream_t s);
+struct LshSearchArgs {
+    GraphDev g;
+    const float* q;        // padded queries [B * pitch]
+    int64_t B;
+    int k;                 // <= 256
+    int T;
+    int64_t n;             // rows the tables hold
+    const uint32_t* codes;        // [n * T]
+    const uint32_t* sorted_code;  // [T * n]
+    const uint32_t* sorted_id;    // [T * n]
+    const uint32_t* qcodes;       // [B * T]
+    int64_t* out_keys;     // [B * k]
+    float* out_dist;       // [B * k]
+    int32_t* out_n;        // [B]
+    int32_t* out_ncand;    // [B] the query's candidate set, before any distance test
+    unsigned long long* stat;  // [0] += candidates (nullable)
+};
+int launch_lsh_search(const LshSearchArgs& a, int lpr, int vpl, hipStream_t s);
+
 // ---- wide exact search (wide.hip): exact top-k past k 256 through the range pipeline ----
 // One chunk of queries: the J-th smallest of each query's ns sample scores (launch_h1_sample's
 // compact matrix) as a distance radius, widened by the certificate's score error; NaN where no

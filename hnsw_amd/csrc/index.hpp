@@ -316,6 +316,32 @@ struct mhnsw_index {
     bool have_reach_timing = false;
     std::vector<int64_t> an_unreach;
     std::mutex an_mu;
+    // LSH index (lsh.hip, lsh_host.cpp; mhnsw_lsh_enable): tables x bits (0: not enabled), the
+    // projections on the host [P * dim] and, zero padded, on the device with their norms (both
+    // empty until the dimension is known), the rows' codes [capn * T], the sorted tables
+    // [T * lsh_tab_n] twice, the queries' codes and candidate counts, the sort's scratch, the
+    // worklist of untrusted signs with its counter and the counters {uncertain pairs, candidates
+    // of the last search}.  Codes of rows [0, lsh_rows) are current; lsh_stale: the tables are
+    // rebuilt by the next LSH search (under lsh_mu, on that search's stream).
+    int lsh_T = 0, lsh_b = 0;
+    uint64_t lsh_seed = 42;
+    bool lsh_user_proj = false;
+    int lsh_pdim = 0;  // the dimension the device projections were written for
+    std::vector<float> lsh_proj;
+    float* lsh_dproj = nullptr;
+    float* lsh_pnorm = nullptr;
+    DevBuf<uint32_t> lsh_codes, lsh_scode, lsh_sid, lsh_qcodes, lsh_key, lsh_val;
+    DevBuf<uint8_t> lsh_tmp;
+    DevBuf<int32_t> lsh_ncand;
+    int64_t lsh_rows = 0, lsh_tab_n = 0;
+    bool lsh_stale = true;
+    uint2* lsh_work = nullptr;
+    uint32_t* lsh_wcnt = nullptr;
+    unsigned long long* lsh_stat = nullptr;
+    int lsh_work_cap = 1 << 18;  // option "lsh_worklist_cap": entries of the worklist a launch may use
+    hipEvent_t lev0 = nullptr, lev1 = nullptr;  // around the last table rebuild
+    bool have_lsh_rebuild = false;
+    std::mutex lsh_mu;
     std::string err;
     mutable std::shared_mutex mu;
 };
@@ -385,7 +411,21 @@ int range_search_impl(mhnsw_index* h, const float* queries, int64_t B, int dim, 
 int range_search_device_impl(mhnsw_index* h, const float* d_queries, int64_t B, int dim, const float* d_radius, int mode, int ef, int64_t cap, int64_t* d_lims, int64_t* d_keys, float* d_dist, hipStream_t s);
 int range_search_filtered_impl(mhnsw_index* h, const float* queries, int64_t B, int dim, const float* radius, int mode, int ef, int route, const int32_t* filter_of, int64_t* out_lims);
 int range_search_filtered_device_impl(mhnsw_index* h, const float* d_queries, int64_t B, int dim, const float* d_radius, int mode, int ef, int route, int filter, int64_t cap, int64_t* d_lims, int64_t* d_keys, float* d_dist, hipStream_t s);
-int import_csr(mhnsw_index* h, int64_t N, int dim, int L, int cap, const int64_t* keys, const float* vecs, const int32_t* deg, const int32_t* adj, const int32_t* entry, const uint8_t* dead);
+// LSH index (lsh_host.cpp).  The lsh_note_* are what a mutation tells it (no-ops until
+// mhnsw_lsh_enable): rows [r0, r1) / the rows d_ids[0 .. m) were written and are hashed now on
+// stream s; every row moved (Compact, Import, Load).  lsh_sync brings codes and tables up to
+// date on stream s before a search reads them.
+constexpr int LSH_WORK_MAX = 1 << 18;
+int lsh_note_rows(mhnsw_index* h, int64_t r0, int64_t r1);
+int lsh_note_ids(mhnsw_index* h, const uint32_t* d_ids, int64_t m, hipStream_t s);
+void lsh_note_all(mhnsw_index* h);
+int lsh_sync(mhnsw_index* h, hipStream_t s);
+int lsh_hash_rows(mhnsw_index* h, const float* X, const float* xnorm, const uint32_t* d_ids, int64_t r0, int64_t r1,
+                  uint32_t* codes, hipStream_t s);
+void lsh_free(mhnsw_index* h);
+int search_lsh_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int64_t* okeys,
+                    float* odist, int32_t* on, int32_t* oncand, hipStream_t s, bool sticky);
+int import_csr(mhnsw_index* h,int64_t N, int dim, int L, int cap, const int64_t* keys, const float* vecs, const int32_t* deg, const int32_t* adj, const int32_t* entry, const uint8_t* dead);
 const char* metric_name(int m);
 int strkey_relabel(mhnsw_index* h);
 int strkey_insert(mhnsw_index* h, const std::string& s);

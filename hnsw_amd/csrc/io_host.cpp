@@ -84,6 +84,7 @@ int import_csr(mhnsw_index* h, int64_t N, int dim, int L, int cap, const int64_t
     LCHK(h, launch_norms(h->vecs, 0, N, h->pitch, h->lpr, h->vpl, h->norms, h->stream));
     if ((r = h16_rows(h, 0, N))) return r;
     h->xsplit_rows = 0;
+    lsh_note_all(h);  // (the LSH configuration and projections are handle state: they stay)
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::vector<int32_t> row;
     h->hlevels.assign(N, 0);

@@ -847,6 +847,63 @@ int search_filtered_exact_impl(mhnsw_index* h, const float* queries, bool on_dev
     return on_scratch(h, s, [&] { return search_filtered_exact(h, c, filter); });
 }
 
+// The LSH search (lsh.go:204; lsh.hip): the exact k nearest among the live rows that share a
+// bucket with the query in some table.  Codes and tables are brought up to date on the call's
+// stream first (lsh_sync); the queries are hashed by the kernel that hashes the rows.
+static int search_lsh(mhnsw_index* h, SearchCall& c, int32_t* oncand) {
+    int r = validate(h);
+    if (r) return r;
+    if (!h->lsh_T) return fail(h, MHNSW_EINVAL, "LSH search before mhnsw_lsh_enable");
+    if ((r = check_args(h, c, MHNSW_MODE_EXACT))) return r;
+    if (c.k > 256) return fail(h, MHNSW_EUNSUPPORTED, "LSH search supports k <= 256");
+    if (c.B <= 0) return 0;
+    if (!h->layers_exist || live_count(h) == 0) {
+        if (c.on_device)
+            HIPCHK(h, hipMemsetAsync(oncand, 0, c.B * 4, c.s));
+        else
+            memset(oncand, 0, c.B * 4);
+        return zero_counts(h, c);
+    }
+    if ((r = lsh_sync(h, c.s)) || (r = stage(h, c))) return r;
+    if ((r = ensure_buf(h, h->qnorm, (size_t)c.B)) || (r = ensure_buf(h, h->lsh_qcodes, (size_t)c.B * h->lsh_T)) ||
+        (!c.on_device && (r = ensure_buf(h, h->lsh_ncand, (size_t)c.B))))
+        return r;
+    if (c.timing) HIPCHK(h, hipEventRecord(h->ev0, c.s));
+    LCHK(h, launch_norms(h->qpad.p, 0, c.B, h->pitch, h->lpr, h->vpl, h->qnorm.p, c.s));
+    if ((r = lsh_hash_rows(h, h->qpad.p, h->qnorm.p, nullptr, 0, c.B, h->lsh_qcodes.p, c.s))) return r;
+    LshSearchArgs a;
+    a.g = graph_view(h);
+    a.g.err = c.errw;
+    a.q = h->qpad.p;
+    a.B = c.B;
+    a.k = c.k;
+    a.T = h->lsh_T;
+    a.n = h->lsh_tab_n;
+    a.codes = h->lsh_codes.p;
+    a.sorted_code = h->lsh_scode.p;
+    a.sorted_id = h->lsh_sid.p;
+    a.qcodes = h->lsh_qcodes.p;
+    a.out_keys = c.dk;
+    a.out_dist = c.dd;
+    a.out_n = c.dn;
+    a.out_ncand = c.on_device ? oncand : h->lsh_ncand.p;
+    a.stat = nullptr;
+    if (!c.sticky) {  // "last_lsh_candidates" describes the last host-pointer search
+        HIPCHK(h, hipMemsetAsync(h->lsh_stat + 1, 0, 8, c.s));
+        a.stat = h->lsh_stat + 1;
+    }
+    LCHK(h, launch_lsh_search(a, h->lpr, h->vpl, c.s));
+    if (c.timing) HIPCHK(h, hipEventRecord(h->ev1, c.s));
+    if (!c.on_device) HIPCHK(h, hipMemcpyAsync(oncand, h->lsh_ncand.p, (size_t)c.B * 4, hipMemcpyDeviceToHost, c.s));
+    return finish(h, c);
+}
+
+int search_lsh_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int64_t* okeys,
+                    float* odist, int32_t* on, int32_t* oncand, hipStream_t s, bool sticky) {
+    SearchCall c{queries, on_device, B, dim, k, okeys, odist, on, nullptr, s, sticky, true};
+    return on_scratch(h, s, [&] { return search_lsh(h, c, oncand); });
+}
+
 int search_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int mode, int ef,
                 const int64_t* entry_key, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool timing,
                 int32_t* out_ids, bool sticky) {

@@ -676,6 +676,69 @@ class Graph:
                                                               C.c_void_p(keys_ptr), C.c_void_p(dist_ptr),
                                                               C.c_void_p(n_ptr), C.c_void_p(stream)))
 
+    # -- LSH index (the reference's hybrid extension, lsh.go; DESIGN.md "LSH index") ------
+    def EnableLSH(self, numTables: int = 4, numBits: int = 8, seed: int = 42, projections=None):
+        """Turn the LSH index on (lsh.go:38 NewLSHIndex): numTables tables of numBits sign
+        bits.  projections None: drawn from SplitMix64(seed) at the first Add's dimension
+        (the default codes differ from Go's, whose math/rand stream is not reproduced);
+        else float32[numTables * numBits, dim].  Rows already stored are hashed at once."""
+        T, b = (numTables if numTables > 0 else 4), (numBits if numBits > 0 else 8)
+        p, d = None, 0
+        if projections is not None:
+            p = _f32(projections)
+            if p.ndim != 2 or p.shape[0] != T * b:
+                raise HnswError(-1, f"projections must be float32[{T * b}, dim], got {p.shape}")
+            d = p.shape[1]
+        self._sync()
+        self._check(load().mhnsw_lsh_enable(self._h, int(numTables), int(numBits), int(seed),
+                                            None if p is None else _ptr(p, C.c_float), d))
+
+    def lsh_hash(self, V) -> np.ndarray:
+        """lsh.go:95 computeHash of arbitrary vectors -> uint32[n, tables]."""
+        v = _f32(V)
+        v = v.reshape(1, -1) if v.ndim == 1 else v
+        out = np.zeros((len(v), self.get_option("lsh_tables")), np.uint32)
+        self._check(load().mhnsw_lsh_hash(self._h, _ptr(v, C.c_float), len(v), v.shape[1], _ptr(out, C.c_uint32)))
+        return out
+
+    def lsh_codes(self) -> np.ndarray:
+        """The stored rows' codes, uint32[rows, tables], in export() row order."""
+        self._sync()
+        N = C.c_int64()
+        self._check(load().mhnsw_export_sizes(self._h, C.byref(N), C.byref(C.c_int()), C.byref(C.c_int()),
+                                              C.byref(C.c_int())))
+        out = np.zeros((N.value, self.get_option("lsh_tables")), np.uint32)
+        self._check(load().mhnsw_lsh_codes(self._h, _ptr(out, C.c_uint32)))
+        return out
+
+    def lsh_projections(self) -> np.ndarray:
+        out = np.zeros((self.get_option("lsh_tables") * self.get_option("lsh_bits"), self.Dims()), np.float32)
+        self._check(load().mhnsw_lsh_projections(self._h, _ptr(out, C.c_float)))
+        return out
+
+    def search_lsh_arrays(self, queries, k: int):
+        """The exact k <= 256 nearest among each query's LSH candidates (the live rows sharing a
+        bucket with it in some table) -> (keys int64[B,k], dist float32[B,k], n int32[B],
+        ncand int32[B]); ncand is the size of the candidate set (lsh.go:170, as a count)."""
+        self._sync()
+        q, ok, od, on = self._search_io(queries, k)
+        B, d = q.shape
+        nc = np.zeros(B, np.int32)
+        self._check(load().mhnsw_search_lsh(self._h, _ptr(q, C.c_float), B, d, int(k), _ptr(ok, C.c_int64),
+                                            _ptr(od, C.c_float), _ptr(on, C.c_int32), _ptr(nc, C.c_int32)))
+        return ok, od, on, nc
+
+    def search_lsh_device(self, q_ptr: int, B: int, dim: int, k: int, keys_ptr: int, dist_ptr: int, n_ptr: int,
+                          ncand_ptr: int, stream: int = 0):
+        """search_lsh_arrays on device buffers, enqueued on `stream` (no host sync)."""
+        self._check(load().mhnsw_search_lsh_device(self._h, C.c_void_p(q_ptr), B, dim, k, C.c_void_p(keys_ptr),
+                                                   C.c_void_p(dist_ptr), C.c_void_p(n_ptr), C.c_void_p(ncand_ptr),
+                                                   C.c_void_p(stream)))
+
+    def SearchLSH(self, near, k: int) -> List[Node]:  # lsh.go:204
+        ok, _, on, _ = self.search_lsh_arrays(np.asarray(near, np.float32).reshape(1, -1), k)
+        return self._nodes(ok[0, : on[0]])
+
     def SearchFiltered(self, near, k: int, filter, ef: int = 0, route: int = 0, mode: int = MODE_BEAM) -> List[Node]:
         q = np.asarray(near, np.float32).reshape(1, -1)
         ok, _, on = self.search_filtered_arrays(q, k, filter, ef=ef, route=route, mode=mode)

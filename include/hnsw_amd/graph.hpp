@@ -427,6 +427,42 @@ class Graph {  // graph.go:305-332
         return range_search(near, radius, filter, true, mode, ef, route);
     }
 
+    // LSH index (mhnsw.h "LSH index"; hybrid/lsh.go NewLSHIndex): numTables tables of numBits
+    // sign bits (<= 0: 4 and 8).  projections empty: drawn from SplitMix64(seed) at the first
+    // Add's dimension; else numTables * numBits vectors of `dim` floats, row-major.  Rows
+    // already stored are hashed at once.
+    Error EnableLSH(int numTables = 4, int numBits = 8, uint64_t seed = 42, const std::vector<float>& projections = {},
+                    int dim = 0) {
+        sync();
+        const int T = numTables > 0 ? numTables : 4, b = numBits > 0 ? numBits : 8;
+        if (!projections.empty() && (dim <= 0 || projections.size() != (size_t)T * b * dim))
+            return Error{"projections must hold " + std::to_string(T * b) + " vectors of dim floats", MHNSW_EINVAL};
+        return make_error(mhnsw_lsh_enable(h_, numTables, numBits, seed, projections.empty() ? nullptr : projections.data(),
+                                           projections.empty() ? 0 : dim),
+                          h_);
+    }
+    // lsh.go:204 Search: the exact k <= 256 nearest among the live rows that share a bucket with
+    // `near` in some table, with their distances; Candidates: the size of that row set
+    struct LSHResult {
+        std::vector<Node<K>> Nodes;
+        std::vector<float> Distances;
+        int Candidates = 0;
+    };
+    std::pair<LSHResult, Error> SearchLSH(const Vector& near, int k) {
+        sync();
+        const size_t kk = k > 0 ? (size_t)k : 1;
+        std::vector<int64_t> keys(kk);
+        std::vector<float> dist(kk);
+        int32_t n = 0, nc = 0;
+        const int rc = mhnsw_search_lsh(h_, near.data(), 1, (int)near.size(), k, keys.data(), dist.data(), &n, &nc);
+        if (rc < 0) return {{}, make_error(rc, h_)};
+        LSHResult out;
+        for (const K& key : Codec::decode(h_, keys.data(), (size_t)n)) out.Nodes.push_back(Node<K>{key, lookup_value(key)});
+        out.Distances.assign(dist.begin(), dist.begin() + n);
+        out.Candidates = nc;
+        return {out, {}};
+    }
+
    private:
     std::pair<std::vector<RangeHit>, Error> range_search(const Vector& near, float radius, const Filter* filter,
                                                          bool filtered, int mode, int ef, int route) {

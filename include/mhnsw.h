@@ -331,6 +331,48 @@ int mhnsw_search_filtered_exact(mhnsw_index *h, const float *queries, int64_t B,
 int mhnsw_search_filtered_exact_device(mhnsw_index *h, const float *d_queries, int64_t B, int dim, int k, int filter,
                                        int64_t *d_keys, float *d_dist, int32_t *d_n, void *stream);
 
+/* ---- LSH index (hnsw-extensions/hybrid/lsh.go; DESIGN.md "LSH index") ----
+ * Random-projection sign codes: `tables` tables of `bits` bits (<= 0: 4 and 8,
+ * lsh.go:38-45; at most 32 each and tables x bits <= 256).  Bit i of table t's
+ * code of a vector x is set iff the canonical f32 dot of x and projection
+ * t bits + i is > 0 (lsh.go:95-116 computeHash, with the engine's summation
+ * order).  An LSH search returns the exact k nearest, by canonical distance and
+ * then row id, among the live rows whose code equals the query's in at least
+ * one table (lsh.go:204 Search over lsh.go:170 GetCandidates); a NaN distance is
+ * never returned.  Works in every build mode.
+ * mhnsw_lsh_enable: turns the index on (lsh.go:38 NewLSHIndex).  projections
+ * NULL: tables x bits vectors uniform in [-1, 1) from a SplitMix64 stream
+ * seeded with `seed` (the reference's 42), drawn at the first Add's dimension
+ * (lsh.go:124); the reference's own stream (Go math/rand) is not reproduced, so
+ * the default codes differ from Go's.  Else float32[tables x bits, dim], the
+ * caller's (MHNSW_EDIM when dim is not the index's).  Rows the handle already
+ * holds are hashed at once; enabling again re-hashes.  The configuration and
+ * the projections survive Compact, Import and Load.
+ * mhnsw_lsh_hash: lsh.go:95 computeHash of n arbitrary vectors, out_codes
+ * uint32[n, tables].  mhnsw_lsh_codes: the stored rows' codes, uint32[rows,
+ * tables], row order of mhnsw_export (lsh.go:142 Add's bucket keys).
+ * mhnsw_lsh_projections: float32[tables x bits, dim] (lsh.go:64
+ * initProjections, unscaled).
+ * mhnsw_search_lsh (lsh.go:204 Search): k <= 256; out_n[b] <= k results,
+ * possibly 0; out_ncand[b] = the size of query b's candidate set (what
+ * lsh.go:170 GetCandidates returns, as a count).  The bucket tables are
+ * rebuilt by the first LSH search after an Add, Replace, Update, Compact,
+ * Import or Load; Delete needs no rebuild.  mhnsw_search_lsh_device: the same
+ * on device buffers, enqueued on `stream` like mhnsw_search_device (lsh.go:204).
+ * Errors: MHNSW_EINVAL "LSH search before mhnsw_lsh_enable", MHNSW_EUNSUPPORTED
+ * "LSH search supports k <= 256", MHNSW_EINVAL for a shape outside the limits.
+ * Read-only options: lsh_tables, lsh_bits, last_lsh_uncertain (signs decided by
+ * the canonical pass since the enable), last_lsh_candidates (of the last
+ * host-pointer search), last_lsh_rebuild_ns. */
+int mhnsw_lsh_enable(mhnsw_index *h, int tables, int bits, uint64_t seed, const float *projections, int dim);
+int mhnsw_lsh_hash(mhnsw_index *h, const float *vecs, int64_t n, int dim, uint32_t *out_codes);
+int mhnsw_lsh_codes(mhnsw_index *h, uint32_t *out);
+int mhnsw_lsh_projections(mhnsw_index *h, float *out);
+int mhnsw_search_lsh(mhnsw_index *h, const float *queries, int64_t B, int dim, int k, int64_t *out_keys,
+                     float *out_dist, int32_t *out_n, int32_t *out_ncand);
+int mhnsw_search_lsh_device(mhnsw_index *h, const float *d_queries, int64_t B, int dim, int k, int64_t *d_keys,
+                            float *d_dist, int32_t *d_n, int32_t *d_ncand, void *stream);
+
 /* ---- Range search: every row within a radius (faiss's range_search; DESIGN.md
  * "Range search") ----
  * For query b with radius radius[b], a row is a hit iff a MHNSW_MODE_EXACT search
