@@ -11,10 +11,10 @@ from .graph import (DOG_QUERY_HACK, Analyzer, CosineDistance, DistanceFunc, Eucl
                     LoadSavedGraph, MakeNode,
                     NewGraph, NewGraphWithConfig, Node, RegisterDistanceFunc, SavedGraph, SplitMix64Rand, Vector,
                     distance_func_to_name, max_level, merge_topk_device, random_level, split_ragged, sweep_device)
-from .adapters import ExactAdapter, ExactIndex, HNSWAdapter, LSHIndex
+from .adapters import ExactAdapter, ExactIndex, HNSWAdapter, LSHIndex, Partitioner
 
 __all__ = [
-    "BUILD_BATCH", "BUILD_COMPAT", "BUILD_FLAT", "ExactIndex", "LSHIndex", "ExactAdapter", "HNSWAdapter", "KEY_STRING", "COSINE", "EUCLIDEAN", "MODE_BEAM", "MODE_COMPAT", "MODE_EXACT", "HnswError",
+    "BUILD_BATCH", "BUILD_COMPAT", "BUILD_FLAT", "ExactIndex", "LSHIndex", "Partitioner", "ExactAdapter", "HNSWAdapter", "KEY_STRING", "COSINE", "EUCLIDEAN", "MODE_BEAM", "MODE_COMPAT", "MODE_EXACT", "HnswError",
     "LIB_PATH", "SIGNATURES", "load", "CosineDistance", "DistanceFunc", "EuclideanDistance", "Filter", "Graph", "MakeNode",
     "NewGraph", "NewGraphWithConfig", "Node", "RegisterDistanceFunc", "Vector", "distance_func_to_name",
     "merge_topk_device", "KEY_INT", "KEY_INT32", "KEY_INT64", "KEY_UINT32", "KEY_UINT64", "LoadSavedGraph",

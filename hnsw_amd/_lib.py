@@ -59,6 +59,16 @@ SIGNATURES = {
     "mhnsw_lsh_projections": (C.c_int, [_vp, _f32p]),
     "mhnsw_search_lsh": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, C.c_int, _i64p, _f32p, _i32p, _i32p]),
     "mhnsw_search_lsh_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "mhnsw_part_enable": (C.c_int, [_vp, C.c_int, C.c_uint64, _f32p, C.c_int]),
+    "mhnsw_part_assign": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, C.c_int, _i32p]),
+    "mhnsw_part_rows": (C.c_int, [_vp, _i32p]),
+    "mhnsw_part_centroids": (C.c_int, [_vp, _f32p]),
+    "mhnsw_part_stats": (C.c_int, [_vp, _i64p]),
+    "mhnsw_part_update_centroids": (C.c_int, [_vp]),
+    "mhnsw_part_rebalance": (C.c_int, [_vp, _i64p]),
+    "mhnsw_part_train": (C.c_int, [_vp, C.c_int, _i64p]),
+    "mhnsw_search_part": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, C.c_int, C.c_int, _i64p, _f32p, _i32p, _i32p]),
+    "mhnsw_search_part_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mhnsw_range_search": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, _f32p, C.c_int, C.c_int, _i64p]),
     "mhnsw_range_results": (C.c_int, [_vp, _i64p, _f32p, C.c_int64]),
     "mhnsw_range_search_device": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, C.c_int64, _vp, _vp,

@@ -146,6 +146,48 @@ class LSHIndex(ExactIndex):
         return [self._g.decode_keys(ok[b, : on[b]]) for b in range(len(on))], od, on, nc
 
 
+class Partitioner(ExactIndex):
+    """hybrid/partitioner.go Partitioner[K] on the GPU: an ExactIndex's flat handle with the
+    partitions enabled (Graph.EnablePartitions).  The reference keeps key sets and is handed
+    the vectors again for UpdateCentroids and Rebalance; here the handle stores them."""
+
+    def __init__(self, numPartitions: int = 10, distance=CosineDistance, centroids=None):
+        super().__init__(distance)
+        self._g.EnablePartitions(numPartitions, centroids=centroids)
+
+    def AssignPartition(self, vector) -> int:  # partitioner.go:83
+        return self._g.AssignPartition(np.asarray(vector, np.float32))
+
+    def AssignVectorToPartition(self, key, vector) -> int:  # partitioner.go:108 (adds or replaces the key)
+        self.Add(key, vector)
+        return self.AssignPartition(vector)
+
+    def GetPartition(self, partitionIdx: int) -> list:  # partitioner.go:121 -> keys
+        if partitionIdx < 0 or partitionIdx >= self._g.get_option("part_count") or self.Len() == 0:
+            return []
+        rows = np.flatnonzero(self._g.partition_rows() == partitionIdx)
+        return self._g.decode_keys(self._g.export()["keys"][rows])
+
+    def RemoveFromPartitions(self, key) -> None:  # partitioner.go:139
+        self.Delete(key)
+
+    def GetPartitionStats(self) -> List[int]:  # partitioner.go:149
+        return self._g.GetPartitionStats()
+
+    def UpdateCentroids(self) -> None:  # partitioner.go:163
+        self._g.UpdateCentroids()
+
+    def Rebalance(self) -> int:  # partitioner.go:210
+        return self._g.Rebalance()
+
+    def Search(self, query, k: int, nprobe: int = 1) -> Tuple[list, List[float]]:
+        """The k nearest among the nprobe nearest partitions' keys -> (keys, distances)."""
+        if self.Len() == 0:
+            return [], []
+        ok, od, on, _ = self._g.search_partitions_arrays(np.asarray(query, np.float32).reshape(1, -1), k, nprobe)
+        return self._g.decode_keys(ok[0, : on[0]]), od[0, : on[0]].tolist()
+
+
 class HNSWAdapter:
     """hybrid/adapter.go HNSWAdapter[K]: SearchableIndex over a Graph."""
 

@@ -1074,6 +1074,9 @@ int add_step(mhnsw_index* h, const int64_t* keys, const float* vecs, bool vecs_o
     if ((r = h16_rows(h, n0, n1))) return r;
     if (rep >= 0) lsh_note_all(h);  // (a replaced key's rows below n0 hold a new vector)
     if ((r = lsh_note_rows(h, n0, n1))) return r;
+    for (int32_t id : {ida, idb})  // partitions: the replaced rows are reassigned now, the new ones lazily
+        if (rep >= 0 && id >= 0 && (r = part_note_range(h, id, id + 1))) return r;
+    part_note_added(h);
     h->layers_exist = true;
     h->n = n1;
     bool published = !defer_keys;
@@ -1303,6 +1306,7 @@ void mhnsw_destroy(mhnsw_index* h) {
     F(h->uids.p);
     F(h->d_repaired);
     lsh_free(h);
+    part_free(h);
     F(h->an_bits.p);
     F(h->an_q.p);
     F(h->an_ids.p);
@@ -1492,6 +1496,12 @@ int mhnsw_set_option(mhnsw_index* h, const char* name, int64_t v) {
     } else if (n == "lsh_worklist_cap") {  // (a small one sends whole launches to the canonical pass: the same codes)
         if (v < 0 || v > LSH_WORK_MAX) return fail(h, MHNSW_EINVAL, "lsh_worklist_cap must be in [0, %d]", LSH_WORK_MAX);
         h->lsh_work_cap = (int)v;
+    } else if (n == "part_worklist_cap") {  // (a small one sends whole launches to the canonical pass: the same partitions)
+        if (v < 0 || v > PART_WORK_MAX) return fail(h, MHNSW_EINVAL, "part_worklist_cap must be in [0, %d]", PART_WORK_MAX);
+        h->part_work_cap = (int)v;
+    } else if (n == "part_force_canon") {
+        if (v != 0 && v != 1) return fail(h, MHNSW_EINVAL, "part_force_canon must be 0 or 1");
+        h->part_force_canon = (int)v;
     } else if (n == "filter_route") {
         if (v < 1 || v > 2048) return fail(h, MHNSW_EINVAL, "filter_route must be in [1, 2048]");
         h->filter_route = (int)v;
@@ -1670,6 +1680,28 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
         float ms = 0.f;
         if (!h->have_lsh_rebuild || hipEventSynchronize(h->lev1) != hipSuccess ||
             hipEventElapsedTime(&ms, h->lev0, h->lev1) != hipSuccess)
+            return MHNSW_EINVAL;
+        *v = (int64_t)std::llround((double)ms * 1e6);
+    }
+    // Partitions: the count (0: not enabled); read-only, from the device (waits for it): the rows
+    // the canonical pass assigned since mhnsw_part_enable, the candidates of the last host-pointer
+    // partition search; the device time of the last list rebuild and of the last Train (HIP events)
+    else if (n == "part_count") *v = h->part_P;
+    else if (n == "part_worklist_cap") *v = h->part_work_cap;
+    else if (n == "part_force_canon") *v = h->part_force_canon;
+    else if (n == "last_part_uncertain" || n == "last_part_candidates") {
+        unsigned long long st[2] = {0, 0};
+        if (h->part_stat && ((h->scr_valid && hipEventSynchronize(h->scr_ev) != hipSuccess) ||
+                             hipStreamSynchronize(h->stream) != hipSuccess ||
+                             hipMemcpy(st, h->part_stat, sizeof st, hipMemcpyDeviceToHost) != hipSuccess))
+            return MHNSW_EDEVICE;
+        *v = (int64_t)st[n == "last_part_uncertain" ? 0 : 1];
+    }
+    else if (n == "last_part_rebuild_ns" || n == "last_part_train_ns") {
+        const int e = n == "last_part_rebuild_ns" ? 0 : 2;
+        float ms = 0.f;
+        if (!(e ? h->have_part_train : h->have_part_rebuild) || hipEventSynchronize(h->pev[e + 1]) != hipSuccess ||
+            hipEventElapsedTime(&ms, h->pev[e], h->pev[e + 1]) != hipSuccess)
             return MHNSW_EINVAL;
         *v = (int64_t)std::llround((double)ms * 1e6);
     }
@@ -2150,6 +2182,7 @@ int mhnsw_replace(mhnsw_index* h, const int64_t* keys, const float* vecs, int64_
                                 h->stream));
     h->xsplit_rows = std::min(h->xsplit_rows, lo);
     if ((r = lsh_note_ids(h, reinterpret_cast<const uint32_t*>(dids), m, h->stream))) return r;
+    if ((r = part_note_ids(h, reinterpret_cast<const uint32_t*>(dids), m, h->stream))) return r;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -2270,6 +2303,7 @@ static int update_impl(mhnsw_index* h, const int64_t* keys, const float* vecs, b
                 LCHK(h, launch_h16_rows_ids(h->vecs, h->norms, d_ids + c0, cnt, h->pitch, h->metric, h->h16,
                                             h->h16aux, h->h16err, s));
             if ((r = lsh_note_ids(h, d_ids + c0, cnt, s))) return r;
+            if ((r = part_note_ids(h, d_ids + c0, cnt, s))) return r;
             // (planes converted so far, in a buffer of the current capacity: rows past xsplit_rows are
             // written to the values the next exact search gives them anyway; an unconverted or
             // outgrown buffer is rebuilt by that search)
@@ -2473,6 +2507,7 @@ int mhnsw_compact(mhnsw_index* h, int64_t* out_removed) {
         hnew[i] = h->hdead[i] ? -1 : (int32_t)live++;
     }
     if (first < 0) return MHNSW_OK;  // nothing deleted: nothing written
+    if ((r = part_flush(h, h->stream))) return r;  // partitions: the pending rows, so that part_of moves whole
     // (the hits a host range search left behind are keys and distances: they stay valid, as
     // they do across Add and Delete)
     ++h->mut_epoch;
@@ -2509,6 +2544,7 @@ int mhnsw_compact(mhnsw_index* h, int64_t* out_removed) {
     arrs.push_back({h->norms, 4});
     arrs.push_back({h->keys, 8});
     arrs.push_back({h->levels, 4});
+    if (h->part_P && h->part_of.p && h->part_rows == n0) arrs.push_back({h->part_of.p, 4});
     for (auto& L : h->layers) {
         arrs.push_back({L.adj, (size_t)L.cap * 4, L.deg});
         arrs.push_back({L.adjd, (size_t)L.cap * 4, L.deg});
@@ -2603,6 +2639,7 @@ int mhnsw_compact(mhnsw_index* h, int64_t* out_removed) {
     // screening copy moved with the rows, and its error maximum over a superset stays valid
     h->xsplit_rows = 0;
     lsh_note_all(h);  // the ids moved: every row is hashed again by the next LSH search
+    part_compacted(h, live);
     if ((r = sync_layer_entries(h))) return r;
     HIPCHK(h, hipStreamSynchronize(s));
     if (out_removed) *out_removed = n0 - live;

@@ -540,6 +540,70 @@ struct LshSearchArgs {
 };
 int launch_lsh_search(const LshSearchArgs& a, int lpr, int vpl, hipStream_t s);
 
+// ---- partitioned index (part.hip): k-means partitions, centroid update, probed search ----
+constexpr int PART_MAX_P = 4096;    // partitions at most
+constexpr int PART_MAX_PROBE = 256; // partitions a search probes at most
+constexpr int PART_PAD_UNIT = 64;   // the centroid matrix holds a multiple of this many rows (zero rows past P)
+constexpr int PART_CHUNK = 256;     // list entries per partial sum of the centroid update
+// The nearest centroid of the rows at positions [r0, r1): position j is row j of X, or row ids[j];
+// the padded vectors of mhnsw_part_assign are X = the query buffer, rows [0, n).  part[row] =
+// the first index of the smallest canonical distance (0 when every distance is NaN).
+struct PartAssignArgs {
+    const float* X;         // [rows * pitch]
+    const float* xnorm;     // [rows] canonical |x|
+    const uint32_t* ids;    // nullable
+    int64_t r0, r1;
+    int pitch, metric;
+    const float* Cn;        // [roundup(P, PART_PAD_UNIT) * pitch] centroids
+    const float* cnorm;     // [roundup(P, PART_PAD_UNIT)] canonical |c|
+    int P;
+    // the error radius of the approximate distance (part_host.cpp part_radius): Euclidean on
+    // squared distances, A = |x|^2 + |c|^2 - 2 x.c within e_rel (|x|^2 + |c|^2) + e_abs, the
+    // canonical sum within a factor 1 +- e_mul of the true one; cosine A = 1 - x.c / (|x| |c|)
+    // within e_abs, products |x| |c| below den_min not trusted
+    float e_rel, e_abs, e_mul, den_min;
+    int32_t* part;          // [rows]
+    uint32_t* work;         // [work_cap] positions of the rows the interval test left open
+    int work_cap;
+    uint32_t* work_cnt;     // [1] rows of this launch (past work_cap: the whole launch is redone canonically)
+    int force;              // test option part_force_canon: every row goes to the canonical pass
+    const uint8_t* dead;    // nullable (the moved count leaves deleted rows out)
+    unsigned long long* stat;   // [0] += rows that went to the canonical pass (nullable)
+    unsigned long long* moved;  // += live rows whose partition changed (nullable: Rebalance only)
+};
+int launch_part_assign(const PartAssignArgs& a, int lpr, int vpl, hipStream_t s);
+// probe order: out[j * m .. j * m + m) = the m nearest centroids of position j by (canonical
+// distance, index), NaN distances after every number
+int launch_part_probe(const float* X, int64_t n, int pitch, int metric, const float* Cn, const float* cnorm, int P, int m,
+                      int32_t* out, int lpr, int vpl, hipStream_t s);
+int part_sort_temp_bytes(int64_t n, size_t* bytes);
+// sorted_id [n] = the rows by (partition, id), the deleted ones last; off [P + 2]: partition p's
+// entries are [off[p], off[p + 1]), off[P] = the live rows
+int launch_part_lists(const int32_t* part, const uint8_t* dead, int P, int64_t n, uint32_t* key, uint32_t* val,
+                      uint32_t* sorted_key, uint32_t* sorted_id, int32_t* off, void* temp, size_t temp_bytes, hipStream_t s);
+int launch_part_stats(const int32_t* part, const uint8_t* dead, int64_t n, int P, unsigned long long* out, hipStream_t s);
+// centroid p = (float)(sum over chunk partials in ascending order / live rows); cbase [P + 1]: the
+// first chunk of each partition; partial [chunks * pitch] f64
+int launch_part_update(const float* X, int pitch, const uint32_t* sorted_id, const int32_t* off, const int32_t* cbase,
+                       int P, int chunks, double* partial, float* Cn, hipStream_t s);
+struct PartSearchArgs {
+    GraphDev g;
+    const float* q;        // padded queries [B * pitch]
+    int64_t B;
+    int k;                 // <= 256
+    int nprobe;
+    const int32_t* probe;      // [B * nprobe] (launch_part_probe)
+    const uint32_t* sorted_id; // [n]
+    const int32_t* off;        // [P + 2]
+    int64_t n;             // rows the lists hold
+    int64_t* out_keys;     // [B * k]
+    float* out_dist;       // [B * k]
+    int32_t* out_n;        // [B]
+    int32_t* out_ncand;    // [B] live rows of the probed partitions
+    unsigned long long* stat;  // [0] += candidates (nullable)
+};
+int launch_part_search(const PartSearchArgs& a, int lpr, int vpl, hipStream_t s);
+
 // ---- wide exact search (wide.hip): exact top-k past k 256 through the range pipeline ----
 // One chunk of queries: the J-th smallest of each query's ns sample scores (launch_h1_sample's
 // compact matrix) as a distance radius, widened by the certificate's score error; NaN where no

@@ -342,6 +342,37 @@ struct mhnsw_index {
     hipEvent_t lev0 = nullptr, lev1 = nullptr;  // around the last table rebuild
     bool have_lsh_rebuild = false;
     std::mutex lsh_mu;
+    // Partitions (part.hip, part_host.cpp; mhnsw_part_enable): P (0: not enabled), the initial
+    // centroids on the host [P * dim] until the dimension is known, then the centroids on the
+    // device, zero padded to whole tiles at the store's pitch, with their norms.  part_of [capn]
+    // is state, not a cache: rows [0, part_rows) hold their stored partition, the rows above are
+    // pending (assigned by part_flush against the centroids as they stand, which no call
+    // changes without flushing first).  The id lists by (partition, id) with their P + 2
+    // offsets are rebuilt lazily (part_stale; under part_mu, on the reading call's stream).
+    // The worklist with its counter, and the counters {uncertain rows, candidates of the last
+    // search, rows the last Rebalance moved}.
+    int part_P = 0;
+    uint64_t part_seed = 42;
+    bool part_user = false;
+    int part_cdim = 0;  // the dimension the device centroids were written for
+    std::vector<float> part_init;
+    float* part_dcent = nullptr;
+    float* part_cnorm = nullptr;
+    DevBuf<int32_t> part_of, part_off, part_probe, part_ncand, part_cbase, part_out;
+    DevBuf<uint32_t> part_key, part_val, part_skey, part_sid;
+    DevBuf<uint8_t> part_tmp;
+    DevBuf<double> part_partial;
+    int64_t part_rows = 0, part_list_n = 0;
+    bool part_stale = true;
+    uint64_t part_list_epoch = ~0ull;  // mut_epoch the lists were built at (a Delete since: they hold dead rows)
+    uint32_t* part_work = nullptr;
+    uint32_t* part_wcnt = nullptr;
+    unsigned long long* part_stat = nullptr;
+    int part_work_cap = 1 << 16;  // option "part_worklist_cap": entries of the worklist a launch may use
+    int part_force_canon = 0;     // test option: every row takes the canonical pass
+    hipEvent_t pev[4] = {};       // around the last list rebuild, around the last Train
+    bool have_part_rebuild = false, have_part_train = false;
+    std::mutex part_mu;
     std::string err;
     mutable std::shared_mutex mu;
 };
@@ -425,6 +456,23 @@ int lsh_hash_rows(mhnsw_index* h, const float* X, const float* xnorm, const uint
 void lsh_free(mhnsw_index* h);
 int search_lsh_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int64_t* okeys,
                     float* odist, int32_t* on, int32_t* oncand, hipStream_t s, bool sticky);
+// Partitions (part_host.cpp).  The part_note_* are what a mutation tells them (no-ops until
+// mhnsw_part_enable): rows were appended (assigned lazily), the rows [r0, r1) / d_ids[0 .. m)
+// hold new vectors and are reassigned now on stream s, every row moved and is reassigned
+// (Import, Load).  part_flush assigns the pending rows; part_sync also brings the lists up to
+// date on stream s (strict: no deleted row left in them).  part_compacted: Compact moved
+// part_of with the rows, `live` of them remain.
+constexpr int PART_WORK_MAX = 1 << 16;
+void part_note_added(mhnsw_index* h);
+int part_note_range(mhnsw_index* h, int64_t r0, int64_t r1);
+int part_note_ids(mhnsw_index* h, const uint32_t* d_ids, int64_t m, hipStream_t s);
+void part_note_all(mhnsw_index* h);
+int part_flush(mhnsw_index* h, hipStream_t s);
+int part_sync(mhnsw_index* h, hipStream_t s, bool strict);
+void part_compacted(mhnsw_index* h, int64_t live);
+void part_free(mhnsw_index* h);
+int search_part_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int nprobe,
+                     int64_t* okeys, float* odist, int32_t* on, int32_t* oncand, hipStream_t s, bool sticky);
 int import_csr(mhnsw_index* h,int64_t N, int dim, int L, int cap, const int64_t* keys, const float* vecs, const int32_t* deg, const int32_t* adj, const int32_t* entry, const uint8_t* dead);
 const char* metric_name(int m);
 int strkey_relabel(mhnsw_index* h);

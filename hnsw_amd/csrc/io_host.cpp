@@ -85,6 +85,7 @@ int import_csr(mhnsw_index* h, int64_t N, int dim, int L, int cap, const int64_t
     if ((r = h16_rows(h, 0, N))) return r;
     h->xsplit_rows = 0;
     lsh_note_all(h);  // (the LSH configuration and projections are handle state: they stay)
+    part_note_all(h);  // (so do the partitions' configuration and centroids: every row is reassigned)
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::vector<int32_t> row;
     h->hlevels.assign(N, 0);

@@ -904,6 +904,65 @@ int search_lsh_impl(mhnsw_index* h, const float* queries, bool on_device, int64_
     return on_scratch(h, s, [&] { return search_lsh(h, c, oncand); });
 }
 
+// The partition search (part.hip): the exact k nearest among the live rows whose stored
+// partition is one of the query's nprobe nearest centroids.  Pending assignments and the lists
+// are brought up to date on the call's stream first (part_sync); the probe order is written
+// by the kernel that serves mhnsw_part_assign.
+static int search_part(mhnsw_index* h, SearchCall& c, int nprobe, int32_t* oncand) {
+    int r = validate(h);
+    if (r) return r;
+    if (!h->part_P) return fail(h, MHNSW_EINVAL, "partition search before mhnsw_part_enable");
+    if ((r = check_args(h, c, MHNSW_MODE_EXACT))) return r;
+    if (c.k > 256) return fail(h, MHNSW_EUNSUPPORTED, "partition search supports k <= 256");
+    if (nprobe < 1 || nprobe > std::min(h->part_P, PART_MAX_PROBE))
+        return fail(h, MHNSW_EINVAL, "nprobe must be in [1, %d], got %d", std::min(h->part_P, PART_MAX_PROBE), nprobe);
+    if (c.B <= 0) return 0;
+    if (!h->layers_exist || live_count(h) == 0) {
+        if (c.on_device)
+            HIPCHK(h, hipMemsetAsync(oncand, 0, c.B * 4, c.s));
+        else
+            memset(oncand, 0, c.B * 4);
+        return zero_counts(h, c);
+    }
+    if ((r = part_sync(h, c.s, false)) || (r = stage(h, c))) return r;
+    if ((r = ensure_buf(h, h->part_probe, (size_t)c.B * nprobe)) ||
+        (!c.on_device && (r = ensure_buf(h, h->part_ncand, (size_t)c.B))))
+        return r;
+    if (c.timing) HIPCHK(h, hipEventRecord(h->ev0, c.s));
+    LCHK(h, launch_part_probe(h->qpad.p, c.B, h->pitch, h->metric, h->part_dcent, h->part_cnorm, h->part_P, nprobe,
+                              h->part_probe.p, h->lpr, h->vpl, c.s));
+    PartSearchArgs a;
+    a.g = graph_view(h);
+    a.g.err = c.errw;
+    a.q = h->qpad.p;
+    a.B = c.B;
+    a.k = c.k;
+    a.nprobe = nprobe;
+    a.probe = h->part_probe.p;
+    a.sorted_id = h->part_sid.p;
+    a.off = h->part_off.p;
+    a.n = h->part_list_n;
+    a.out_keys = c.dk;
+    a.out_dist = c.dd;
+    a.out_n = c.dn;
+    a.out_ncand = c.on_device ? oncand : h->part_ncand.p;
+    a.stat = nullptr;
+    if (!c.sticky) {  // "last_part_candidates" describes the last host-pointer search
+        HIPCHK(h, hipMemsetAsync(h->part_stat + 1, 0, 8, c.s));
+        a.stat = h->part_stat + 1;
+    }
+    LCHK(h, launch_part_search(a, h->lpr, h->vpl, c.s));
+    if (c.timing) HIPCHK(h, hipEventRecord(h->ev1, c.s));
+    if (!c.on_device) HIPCHK(h, hipMemcpyAsync(oncand, h->part_ncand.p, (size_t)c.B * 4, hipMemcpyDeviceToHost, c.s));
+    return finish(h, c);
+}
+
+int search_part_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int nprobe,
+                     int64_t* okeys, float* odist, int32_t* on, int32_t* oncand, hipStream_t s, bool sticky) {
+    SearchCall c{queries, on_device, B, dim, k, okeys, odist, on, nullptr, s, sticky, true};
+    return on_scratch(h, s, [&] { return search_part(h, c, nprobe, oncand); });
+}
+
 int search_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int mode, int ef,
                 const int64_t* entry_key, int64_t* okeys, float* odist, int32_t* on, hipStream_t s, bool timing,
                 int32_t* out_ids, bool sticky) {

@@ -739,6 +739,99 @@ class Graph:
         ok, _, on, _ = self.search_lsh_arrays(np.asarray(near, np.float32).reshape(1, -1), k)
         return self._nodes(ok[0, : on[0]])
 
+    # -- partitions (the reference's hybrid extension, partitioner.go; DESIGN.md "Partitions") ------
+    def EnablePartitions(self, numPartitions: int = 10, centroids=None, seed: int = 42):
+        """Turn the partitions on (partitioner.go:31 NewPartitioner).  centroids None: drawn
+        from SplitMix64(seed) at the first Add's dimension as partitioner.go:58-78 draws them
+        (Go's math/rand stream is not reproduced); else float32[numPartitions, dim], e.g. rows
+        taken from Lookup.  Rows already stored are assigned at once."""
+        P = numPartitions if numPartitions > 0 else 10
+        c, d = None, 0
+        if centroids is not None:
+            c = _f32(centroids)
+            if c.ndim != 2 or c.shape[0] != P:
+                raise HnswError(-1, f"centroids must be float32[{P}, dim], got {c.shape}")
+            d = c.shape[1]
+        self._sync()
+        self._check(load().mhnsw_part_enable(self._h, int(numPartitions), int(seed),
+                                             None if c is None else _ptr(c, C.c_float), d))
+
+    def assign_partitions(self, X, nprobe: int = 1) -> np.ndarray:
+        """The first nprobe entries of each vector's probe order (centroids by (canonical
+        distance, index), NaN last) -> int32[n, nprobe]."""
+        v = _f32(X)
+        v = v.reshape(1, -1) if v.ndim == 1 else v
+        out = np.zeros((len(v), int(nprobe)), np.int32)
+        self._check(load().mhnsw_part_assign(self._h, _ptr(v, C.c_float), len(v), v.shape[1], int(nprobe),
+                                             _ptr(out, C.c_int32)))
+        return out
+
+    def AssignPartition(self, vec) -> int:  # partitioner.go:83
+        return int(self.assign_partitions(vec)[0, 0])
+
+    def partition_rows(self) -> np.ndarray:
+        """The stored rows' partitions, int32[rows] in export() row order, -1 for a deleted row."""
+        self._sync()
+        N = C.c_int64()
+        self._check(load().mhnsw_export_sizes(self._h, C.byref(N), C.byref(C.c_int()), C.byref(C.c_int()),
+                                              C.byref(C.c_int())))
+        out = np.zeros(N.value, np.int32)
+        self._check(load().mhnsw_part_rows(self._h, _ptr(out, C.c_int32)))
+        return out
+
+    def partition_centroids(self) -> np.ndarray:
+        out = np.zeros((self.get_option("part_count"), self.Dims()), np.float32)
+        self._check(load().mhnsw_part_centroids(self._h, _ptr(out, C.c_float)))
+        return out
+
+    def GetPartitionStats(self) -> List[int]:  # partitioner.go:149: live rows per partition
+        self._sync()
+        out = np.zeros(self.get_option("part_count"), np.int64)
+        self._check(load().mhnsw_part_stats(self._h, _ptr(out, C.c_int64)))
+        return out.tolist()
+
+    def UpdateCentroids(self) -> None:  # partitioner.go:163
+        self._sync()
+        self._check(load().mhnsw_part_update_centroids(self._h))
+
+    def Rebalance(self) -> int:  # partitioner.go:210 -> the rows whose partition changed
+        self._sync()
+        moved = C.c_int64()
+        self._check(load().mhnsw_part_rebalance(self._h, C.byref(moved)))
+        return moved.value
+
+    def TrainPartitions(self, iters: int) -> int:
+        """iters times (UpdateCentroids, Rebalance), stopping after a Rebalance that moved no
+        row -> the rows the last Rebalance moved."""
+        self._sync()
+        moved = C.c_int64()
+        self._check(load().mhnsw_part_train(self._h, int(iters), C.byref(moved)))
+        return moved.value
+
+    def search_partitions_arrays(self, queries, k: int, nprobe: int = 1):
+        """The exact k <= 256 nearest among the live rows of each query's nprobe nearest
+        partitions -> (keys int64[B,k], dist float32[B,k], n int32[B], ncand int32[B]); ncand
+        is the number of those rows.  nprobe = the partition count: the MODE_EXACT result."""
+        self._sync()
+        q, ok, od, on = self._search_io(queries, k)
+        B, d = q.shape
+        nc = np.zeros(B, np.int32)
+        self._check(load().mhnsw_search_part(self._h, _ptr(q, C.c_float), B, d, int(k), int(nprobe),
+                                             _ptr(ok, C.c_int64), _ptr(od, C.c_float), _ptr(on, C.c_int32),
+                                             _ptr(nc, C.c_int32)))
+        return ok, od, on, nc
+
+    def search_partitions_device(self, q_ptr: int, B: int, dim: int, k: int, nprobe: int, keys_ptr: int, dist_ptr: int,
+                                 n_ptr: int, ncand_ptr: int, stream: int = 0):
+        """search_partitions_arrays on device buffers, enqueued on `stream` (no host sync)."""
+        self._check(load().mhnsw_search_part_device(self._h, C.c_void_p(q_ptr), B, dim, k, nprobe,
+                                                    C.c_void_p(keys_ptr), C.c_void_p(dist_ptr), C.c_void_p(n_ptr),
+                                                    C.c_void_p(ncand_ptr), C.c_void_p(stream)))
+
+    def SearchPartitions(self, near, k: int, nprobe: int = 1) -> List[Node]:
+        ok, _, on, _ = self.search_partitions_arrays(np.asarray(near, np.float32).reshape(1, -1), k, nprobe)
+        return self._nodes(ok[0, : on[0]])
+
     def SearchFiltered(self, near, k: int, filter, ef: int = 0, route: int = 0, mode: int = MODE_BEAM) -> List[Node]:
         q = np.asarray(near, np.float32).reshape(1, -1)
         ok, _, on = self.search_filtered_arrays(q, k, filter, ef=ef, route=route, mode=mode)

@@ -463,6 +463,60 @@ class Graph {  // graph.go:305-332
         return {out, {}};
     }
 
+    // Partitions (mhnsw.h "Partitions"; hybrid/partitioner.go NewPartitioner): numPartitions
+    // centroids (<= 0: 10).  centroids empty: drawn from SplitMix64(seed) at the first Add's
+    // dimension; else numPartitions vectors of `dim` floats, row-major.  Rows already stored
+    // are assigned at once.
+    Error EnablePartitions(int numPartitions = 10, const std::vector<float>& centroids = {}, int dim = 0,
+                           uint64_t seed = 42) {
+        sync();
+        const int P = numPartitions > 0 ? numPartitions : 10;
+        if (!centroids.empty() && (dim <= 0 || centroids.size() != (size_t)P * dim))
+            return Error{"centroids must hold " + std::to_string(P) + " vectors of dim floats", MHNSW_EINVAL};
+        return make_error(mhnsw_part_enable(h_, numPartitions, seed, centroids.empty() ? nullptr : centroids.data(),
+                                            centroids.empty() ? 0 : dim),
+                          h_);
+    }
+    // partitioner.go:83 AssignPartition: the nearest centroid (ties to the lowest index)
+    std::pair<int, Error> AssignPartition(const Vector& v) {
+        sync();
+        int32_t p = 0;
+        const int rc = mhnsw_part_assign(h_, v.data(), 1, (int)v.size(), 1, &p);
+        return {(int)p, make_error(rc, h_)};
+    }
+    // partitioner.go:149 GetPartitionStats: live rows per partition
+    std::pair<std::vector<int64_t>, Error> PartitionStats() {
+        sync();
+        int64_t P = 0;
+        int rc = mhnsw_get_option(h_, "part_count", &P);
+        std::vector<int64_t> out((size_t)(P > 0 ? P : 1), 0);
+        if (rc >= 0) rc = mhnsw_part_stats(h_, out.data());
+        out.resize((size_t)P);
+        return {out, make_error(rc, h_)};
+    }
+    // iters times (partitioner.go:163 UpdateCentroids, :210 Rebalance) -> the rows the last Rebalance moved
+    std::pair<int64_t, Error> TrainPartitions(int iters) {
+        sync();
+        int64_t moved = 0;
+        const int rc = mhnsw_part_train(h_, iters, &moved);
+        return {moved, make_error(rc, h_)};
+    }
+    // the exact k <= 256 nearest among the live rows of the nprobe nearest partitions (LSHResult's shape)
+    std::pair<LSHResult, Error> SearchPartitions(const Vector& near, int k, int nprobe = 1) {
+        sync();
+        const size_t kk = k > 0 ? (size_t)k : 1;
+        std::vector<int64_t> keys(kk);
+        std::vector<float> dist(kk);
+        int32_t n = 0, nc = 0;
+        const int rc = mhnsw_search_part(h_, near.data(), 1, (int)near.size(), k, nprobe, keys.data(), dist.data(), &n, &nc);
+        if (rc < 0) return {{}, make_error(rc, h_)};
+        LSHResult out;
+        for (const K& key : Codec::decode(h_, keys.data(), (size_t)n)) out.Nodes.push_back(Node<K>{key, lookup_value(key)});
+        out.Distances.assign(dist.begin(), dist.begin() + n);
+        out.Candidates = nc;
+        return {out, {}};
+    }
+
    private:
     std::pair<std::vector<RangeHit>, Error> range_search(const Vector& near, float radius, const Filter* filter,
                                                          bool filtered, int mode, int ef, int route) {

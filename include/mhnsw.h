@@ -373,6 +373,72 @@ int mhnsw_search_lsh(mhnsw_index *h, const float *queries, int64_t B, int dim, i
 int mhnsw_search_lsh_device(mhnsw_index *h, const float *d_queries, int64_t B, int dim, int k, int64_t *d_keys,
                             float *d_dist, int32_t *d_n, int32_t *d_ncand, void *stream);
 
+/* ---- Partitions (hnsw-extensions/hybrid/partitioner.go; DESIGN.md "Partitions") ----
+ * P centroids (default 10 for partitions <= 0, partitioner.go:32-34; at most
+ * 4096).  The canonical distance is what mhnsw_distance returns, the vector first
+ * and the centroid second (partitioner.go:97).  The probe order of a vector is
+ * the centroid indices by (canonical distance, index), NaN after every number;
+ * its partition is the first of them: the nearest centroid, ties to the lowest
+ * index, partition 0 when every distance is NaN.  This is partitioner.go:92-104
+ * except for distances >= 1e10, the reference's initial bestDistance, which the
+ * reference sends to partition 0 and the engine does not.  A stored row's
+ * partition is its assignment against the centroids as they stood at the later
+ * of its Add, its last Update or Replace, and the last Rebalance
+ * (partitioner.go:108 AssignVectorToPartition, :210 Rebalance); Import and Load
+ * reassign every row; Compact moves the assignments with the rows; a deleted row
+ * is in no partition.
+ * mhnsw_part_enable: turns the partitions on (partitioner.go:31 NewPartitioner).
+ * centroids float32[partitions, dim], or NULL: drawn at the first Add's dimension
+ * from a SplitMix64 stream of `seed` as partitioner.go:58-78 draws them (element
+ * (float)(u * 2 - 1), the row scaled by (float)(1 / (double)sum of squares));
+ * the reference's own stream (Go math/rand) is not reproduced.  On a handle that
+ * holds rows every row is assigned now.
+ * mhnsw_part_assign: partitioner.go:83 AssignPartition of n arbitrary vectors,
+ * out_parts int32[n, nprobe]: the first nprobe entries of each probe order.
+ * mhnsw_part_rows: the stored rows' partitions, int32[rows], -1 for a deleted
+ * row, row order of mhnsw_export (partitioner.go:108, the partitions' key sets).
+ * mhnsw_part_centroids: float32[partitions, dim].
+ * mhnsw_part_stats: live rows per partition, int64[partitions]
+ * (partitioner.go:149 GetPartitionStats).
+ * mhnsw_part_update_centroids (partitioner.go:163-206 UpdateCentroids): centroid p
+ * becomes the mean of the live rows assigned to p, a partition without one keeps
+ * its centroid.  The order of the sum is fixed: f64, the partition's rows by
+ * ascending row id in chunks of 256, each chunk summed sequentially, the chunk
+ * sums added in ascending order, the element (float)(sum / count).
+ * mhnsw_part_rebalance (partitioner.go:210-222 Rebalance): every live row is
+ * reassigned against the current centroids; out_moved the rows whose partition
+ * changed.  mhnsw_part_train: iters times (update_centroids, rebalance), stopping
+ * after a rebalance that moved no row; out_moved of the last one.  All three
+ * first complete the pending assignments against the centroids as they stand.
+ * mhnsw_search_part: the reference's hybrid index never searches its partitions
+ * (hybrid.go:266-267); this does.  k <= 256, 1 <= nprobe <= min(partitions, 256):
+ * out_n[b] <= k results, the k nearest by (canonical distance, row id) among the
+ * live rows whose partition is among the query's first nprobe probes, never a NaN
+ * distance; out_ncand[b] the live rows of those partitions.  With nprobe =
+ * partitions the result is the MHNSW_MODE_EXACT search's.  The id lists are
+ * rebuilt by the first call that needs them after an Add, Replace, Update,
+ * Rebalance, Compact, Import or Load; Delete needs no rebuild.
+ * mhnsw_search_part_device: the same on device buffers, enqueued on `stream`
+ * like mhnsw_search_device.
+ * Errors: MHNSW_EINVAL "partition search before mhnsw_part_enable", MHNSW_EINVAL
+ * for partitions or nprobe outside their limits, MHNSW_EUNSUPPORTED "partition
+ * search supports k <= 256", MHNSW_EDIM for centroids of another dimension.
+ * Read-only options: part_count, last_part_uncertain (rows assigned by the
+ * canonical pass since the enable), last_part_candidates (of the last
+ * host-pointer search), last_part_rebuild_ns, last_part_train_ns. */
+int mhnsw_part_enable(mhnsw_index *h, int partitions, uint64_t seed, const float *centroids, int dim);
+int mhnsw_part_assign(mhnsw_index *h, const float *vecs, int64_t n, int dim, int nprobe, int32_t *out_parts);
+int mhnsw_part_rows(mhnsw_index *h, int32_t *out);
+int mhnsw_part_centroids(mhnsw_index *h, float *out);
+int mhnsw_part_stats(mhnsw_index *h, int64_t *out);
+int mhnsw_part_update_centroids(mhnsw_index *h);
+int mhnsw_part_rebalance(mhnsw_index *h, int64_t *out_moved);
+int mhnsw_part_train(mhnsw_index *h, int iters, int64_t *out_moved);
+int mhnsw_search_part(mhnsw_index *h, const float *queries, int64_t B, int dim, int k, int nprobe, int64_t *out_keys,
+                      float *out_dist, int32_t *out_n, int32_t *out_ncand);
+int mhnsw_search_part_device(mhnsw_index *h, const float *d_queries, int64_t B, int dim, int k, int nprobe,
+                             int64_t *d_keys, float *d_dist, int32_t *d_n, int32_t *d_ncand, void *stream);
+
 /* ---- Range search: every row within a radius (faiss's range_search; DESIGN.md
  * "Range search") ----
  * For query b with radius radius[b], a row is a hit iff a MHNSW_MODE_EXACT search
