@@ -1502,6 +1502,18 @@ int mhnsw_set_option(mhnsw_index* h, const char* name, int64_t v) {
     } else if (n == "part_force_canon") {
         if (v != 0 && v != 1) return fail(h, MHNSW_EINVAL, "part_force_canon must be 0 or 1");
         h->part_force_canon = (int)v;
+    } else if (n == "part_scan") {
+        if (v != 0 && v != 1) return fail(h, MHNSW_EINVAL, "part_scan must be 0 or 1");
+        h->part_scan = (int)v;
+    } else if (n == "part_scan_min_b") {
+        if (v < 1 || v > INT32_MAX) return fail(h, MHNSW_EINVAL, "part_scan_min_b must be >= 1");
+        h->part_scan_min_b = (int)v;
+    } else if (n == "part_scan_seed") {  // (a search covers at most nprobe - 1 with it)
+        if (v < 1 || v >= PART_MAX_PROBE) return fail(h, MHNSW_EINVAL, "part_scan_seed must be in [1, %d]", PART_MAX_PROBE - 1);
+        h->part_scan_seed = (int)v;
+    } else if (n == "part_scan_room") {
+        if (v < 1 || v > (1 << 20)) return fail(h, MHNSW_EINVAL, "part_scan_room must be in [1, %d]", 1 << 20);
+        h->part_scan_room = (int)v;
     } else if (n == "filter_route") {
         if (v < 1 || v > 2048) return fail(h, MHNSW_EINVAL, "filter_route must be in [1, 2048]");
         h->filter_route = (int)v;
@@ -1702,6 +1714,30 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
         float ms = 0.f;
         if (!(e ? h->have_part_train : h->have_part_rebuild) || hipEventSynchronize(h->pev[e + 1]) != hipSuccess ||
             hipEventElapsedTime(&ms, h->pev[e], h->pev[e + 1]) != hipSuccess)
+            return MHNSW_EINVAL;
+        *v = (int64_t)std::llround((double)ms * 1e6);
+    }
+    // The partition-major scan: its options; read-only, of the last partition search: the queries
+    // sent through the scan (0: the walk ran), from the device (waits for it) the survivors the
+    // finish ranked and the queries it answered by the walk, and the device time of the
+    // inversion and the scan kernel (HIP events)
+    else if (n == "part_scan") *v = h->part_scan;
+    else if (n == "part_scan_min_b") *v = h->part_scan_min_b;
+    else if (n == "part_scan_seed") *v = h->part_scan_seed;
+    else if (n == "part_scan_room") *v = h->part_scan_room;
+    else if (n == "last_part_scan_queries") *v = h->part_scan_queries;
+    else if (n == "last_part_scan_pairs" || n == "last_part_scan_fallback_queries") {
+        unsigned long long st[2] = {0, 0};
+        if (h->part_scan_queries && ((h->scr_valid && hipEventSynchronize(h->scr_ev) != hipSuccess) ||
+                                     hipStreamSynchronize(h->stream) != hipSuccess ||
+                                     hipMemcpy(st, h->ps_stat.p, sizeof st, hipMemcpyDeviceToHost) != hipSuccess))
+            return MHNSW_EDEVICE;
+        *v = (int64_t)st[n == "last_part_scan_pairs" ? 0 : 1];
+    }
+    else if (n == "last_part_scan_ns") {
+        float ms = 0.f;
+        if (!h->have_part_scan_timing || hipEventSynchronize(h->psev[1]) != hipSuccess ||
+            hipEventElapsedTime(&ms, h->psev[0], h->psev[1]) != hipSuccess)
             return MHNSW_EINVAL;
         *v = (int64_t)std::llround((double)ms * 1e6);
     }

@@ -604,6 +604,48 @@ struct PartSearchArgs {
 };
 int launch_part_search(const PartSearchArgs& a, int lpr, int vpl, hipStream_t s);
 
+// ---- the partition-major scan (part_scan.hip): the same search, the probed rows scored once per
+// query tile on the fp16 MFMA (DESIGN.md §6 "Partition scan").  The four launches in order:
+// seed (the walk over each query's first `seed` probes -> its list and score threshold), invert
+// (the other probes as (partition, query) pairs by partition, the live rows per partition, the
+// items' prefix), tiles (k_part_scan: survivors per query), finish (the survivors ranked
+// canonically onto the seed list; a query without a threshold, or whose survivors overflowed,
+// walks all its probes).
+constexpr int PSCAN_BM = 64, PSCAN_BN = 128;  // k_part_scan's tile: queries x rows
+struct PartScanArgs {
+    PartSearchArgs s;       // the walk's arguments and the call's outputs
+    int P, seed, room;      // partitions; probes the seed walk covers; survivor slots per query
+    int pitch;
+    const float* qnorm;     // [B] canonical |q|
+    const float* qinv;      // [B] fp16 unscale of the queries (launch_split_h16)
+    const uint16_t* Qh;     // the queries' K-blocked fp16 plane, ldQ rows per K-block
+    int64_t ldQ;
+    const uint16_t* Xh;     // the rows', ldX rows per K-block
+    int64_t ldX;
+    const float* xinv;      // [capn]
+    CertArgs c;             // eps_cos / eps_dot / c_l2 / xmax / xerr / qerr
+    float* seed_d;          // [B * k] the seed lists
+    uint32_t* seed_i;
+    float* thr;             // [B] score threshold; NaN: the query walks
+    uint32_t* pkey;         // [B * (nprobe - seed)] pairs: partition (P: the query walks), query
+    uint32_t* pval;
+    uint32_t* skey;         // the pairs by partition
+    uint32_t* sval;
+    int32_t* poff;          // [P + 2] partition p's queries are sval[poff[p] .. poff[p + 1])
+    int32_t* ibase;         // [P + 1] the first item of partition p; ibase[P]: the items
+    int32_t* live;          // [P] live rows of each list
+    uint32_t* scnt;         // [B] survivors appended (past room: counted only)
+    uint32_t* surv;         // [B * room] row ids
+    unsigned long long* stat;  // [0] += survivors ranked, [1] += queries that walked
+    void* temp;
+    size_t temp_bytes;
+};
+int part_scan_temp_bytes(int64_t pairs, size_t* bytes);
+int launch_part_scan_seed(const PartScanArgs& a, int lpr, int vpl, hipStream_t s);
+int launch_part_scan_invert(const PartScanArgs& a, hipStream_t s);
+int launch_part_scan_tiles(const PartScanArgs& a, hipStream_t s);
+int launch_part_scan_finish(const PartScanArgs& a, int lpr, int vpl, hipStream_t s);
+
 // ---- wide exact search (wide.hip): exact top-k past k 256 through the range pipeline ----
 // One chunk of queries: the J-th smallest of each query's ns sample scores (launch_h1_sample's
 // compact matrix) as a distance radius, widened by the certificate's score error; NaN where no

@@ -27,6 +27,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "cert.hpp"
 #include "device_search.hpp"
 #include "engine.hpp"
 
@@ -299,12 +300,7 @@ int launch_max_norm(const float* norms, int64_t n, float* out, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// Split-operand GEMM modes (planes of A = queries, B = rows, all K-blocked by 16):
-//   RING_X3 bf16x3     q.x ~ ql.xh + qh.xl + qh.xh  (A hi+lo, B hi+lo)
-//   RING_H2 fp16 2-pr. q.x ~ ql.xh + qh.xh          (A hi+lo, B hi; rows rounded once)
-//   RING_H1 fp16 1-pr. q.x ~ qh.xh                  (A hi,    B hi; both rounded once)
-enum { RING_X3 = 0, RING_H2 = 1, RING_H1 = 2 };
-
+// (the split-operand GEMM modes RING_X3 / RING_H2 / RING_H1 and split_score: cert.hpp)
 // Block tile BM (queries) x BN (rows) = (WAVES_M*TM*32) x (WAVES_N*TN*32).  One
 // ring stage = S K-blocks of 16.  LDS image of one K-block: [A hi][A lo][B hi]
 // [B lo] (planes the mode uses), each rows x 16 halves (two 16-B chunks per
@@ -397,18 +393,6 @@ __device__ __forceinline__ void ring_stage(const uint16_t* buf, f32x16 (&acc)[TM
 #pragma unroll
     for (int sb = 0; sb < S; ++sb) ring_mma<T, MODE, TM, TN>(f[sb], acc);
     __builtin_amdgcn_s_setprio(0);
-}
-
-// the score of one (query, row) pair from its accumulator -- the one formula
-// every consumer of split scores uses (write epilogue, candidate select), so
-// a score is the same float wherever it is computed.  Outside the fp16 bound
-// (NaN unscale): -inf, always preselected / never certified.
-__device__ __forceinline__ float split_score(int mode, int metric, float acc, float xi, float qi, float qn, float xn) {
-    const float dot = mode != RING_X3 ? acc * xi * qi : acc;
-    float sc = metric == COSINE ? 1.0f - dot / (qn * xn) : fmaf(-2.f, dot, qn * qn + xn * xn);
-    if (!(sc == sc)) sc = __int_as_float(0x7f800000);
-    if (mode != RING_X3 && !(xi == xi && qi == qi)) sc = -__int_as_float(0x7f800000);
-    return sc;
 }
 
 // Staged by LDS-DMA (global_load_lds_dwordx4: 1 KiB per wave instruction

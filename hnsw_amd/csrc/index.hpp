@@ -372,6 +372,20 @@ struct mhnsw_index {
     int part_force_canon = 0;     // test option: every row takes the canonical pass
     hipEvent_t pev[4] = {};       // around the last list rebuild, around the last Train
     bool have_part_rebuild = false, have_part_train = false;
+    // The partition-major scan (part_scan.hip; part_host.cpp part_scan_search): the options
+    // "part_scan", "part_scan_min_b", "part_scan_seed", "part_scan_room"; the seed lists, the
+    // thresholds, the (partition, query) pairs and their sorted copy, the per-partition tables,
+    // the survivors with their counts, the counters {survivors ranked, queries that walked};
+    // the queries the last partition search sent through the scan; events around its kernels.
+    int part_scan = 0, part_scan_min_b = 64, part_scan_seed = 1, part_scan_room = 1024;
+    DevBuf<float> ps_seed_d, ps_thr;
+    DevBuf<uint32_t> ps_seed_i, ps_pairs, ps_scnt, ps_surv;
+    DevBuf<int32_t> ps_tab;
+    DevBuf<uint8_t> ps_tmp;
+    DevBuf<unsigned long long> ps_stat;
+    int64_t part_scan_queries = 0;
+    hipEvent_t psev[2] = {};
+    bool have_part_scan_timing = false;
     std::mutex part_mu;
     std::string err;
     mutable std::shared_mutex mu;
@@ -471,6 +485,13 @@ int part_flush(mhnsw_index* h, hipStream_t s);
 int part_sync(mhnsw_index* h, hipStream_t s, bool strict);
 void part_compacted(mhnsw_index* h, int64_t live);
 void part_free(mhnsw_index* h);
+// the partition search's ranking by the partition-major scan instead of launch_part_search (a:
+// the walk's arguments, complete); part_scan_wanted: the options and the shape ask for it
+bool part_scan_wanted(const mhnsw_index* h, int64_t B, int nprobe);
+int part_scan_search(mhnsw_index* h, const mh::PartSearchArgs& a, bool timing, hipStream_t s);
+// the certificate's constants for scores of `products` MFMA products per element whose operand
+// split loses at most e_split (search_host.cpp: exact_prepare's arithmetic)
+void exact_cert_consts(const mhnsw_index* h, double products, double e_split, mh::CertArgs& cert);
 int search_part_impl(mhnsw_index* h, const float* queries, bool on_device, int64_t B, int dim, int k, int nprobe,
                      int64_t* okeys, float* odist, int32_t* on, int32_t* oncand, hipStream_t s, bool sticky);
 int import_csr(mhnsw_index* h,int64_t N, int dim, int L, int cap, const int64_t* keys, const float* vecs, const int32_t* deg, const int32_t* adj, const int32_t* entry, const uint8_t* dead);

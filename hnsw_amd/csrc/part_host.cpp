@@ -80,7 +80,23 @@ void part_free(mhnsw_index* h) {
     F(h->part_partial.p);
     h->part_of.n = h->part_off.n = h->part_probe.n = h->part_ncand.n = h->part_cbase.n = h->part_out.n = 0;
     h->part_key.n = h->part_val.n = h->part_skey.n = h->part_sid.n = h->part_tmp.n = h->part_partial.n = 0;
+    F(h->ps_seed_d.p);
+    F(h->ps_thr.p);
+    F(h->ps_seed_i.p);
+    F(h->ps_pairs.p);
+    F(h->ps_scnt.p);
+    F(h->ps_surv.p);
+    F(h->ps_tab.p);
+    F(h->ps_tmp.p);
+    F(h->ps_stat.p);
+    h->ps_seed_d.n = h->ps_thr.n = h->ps_seed_i.n = h->ps_pairs.n = h->ps_scnt.n = h->ps_surv.n = 0;
+    h->ps_tab.n = h->ps_tmp.n = h->ps_stat.n = 0;
+    h->have_part_scan_timing = false;
     for (hipEvent_t& e : h->pev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    for (hipEvent_t& e : h->psev) {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
     }
@@ -302,6 +318,101 @@ static int part_rebalance(mhnsw_index* h, int64_t* moved) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->part_stale = true;
     *moved = (int64_t)mv;
+    return 0;
+}
+
+// ---- the partition-major scan (part_scan.hip; DESIGN.md §6 "Partition scan") ----
+// Option "part_scan": from part_scan_min_b queries and two probes on.  (The items' count is a
+// 32-bit prefix: a shape whose bound on it does not fit keeps the walk.)
+bool part_scan_wanted(const mhnsw_index* h, int64_t B, int nprobe) {
+    if (!h->part_scan || nprobe < 2 || B < h->part_scan_min_b) return false;
+    const int64_t qt = B * nprobe / PSCAN_BM + h->part_P, rt = h->part_list_n / PSCAN_BN + 1;
+    return B * nprobe < ((int64_t)1 << 31) && qt * rt < ((int64_t)1 << 31);
+}
+
+// The ranking of a partition search whose probe order is written (a: launch_part_search's
+// arguments), all on s from the handle's buffers, no host synchronisation.  The scores run on
+// the exact path's fp16 row plane (brought up to date here as exact_run does) at precision 3,
+// whatever exact_precision the handle keeps.
+int part_scan_search(mhnsw_index* h, const PartSearchArgs& a, bool timing, hipStream_t s) {
+    int r;
+    const int64_t B = a.B;
+    const int nprobe = a.nprobe, P = h->part_P;
+    const int seed = std::min(h->part_scan_seed, nprobe - 1), room = h->part_scan_room;
+    const int64_t pairs = B * (nprobe - seed);
+    size_t tb = 0;
+    if (part_scan_temp_bytes(pairs, &tb)) return fail(h, MHNSW_EDEVICE, "radix sort sizing failed");
+    const int64_t plane = h->capn * h->pitch;
+    if (h->xsplit.n < (size_t)plane * 2 || h->xsplit_plane != plane || h->xsplit_kind != 2) {
+        if ((r = ensure_buf(h, h->xsplit, (size_t)plane * 2))) return r;
+        h->xsplit_rows = 0;
+        h->xsplit_plane = plane;
+        h->xsplit_kind = 2;
+    }
+    if ((r = ensure_buf(h, h->xinv, (size_t)h->capn)) || (r = ensure_buf(h, h->xerr, 1)) || (r = ensure_buf(h, h->qerr, 1)) ||
+        (r = ensure_buf(h, h->xmaxn, 1)) || (r = ensure_buf(h, h->qnorm, (size_t)B)) || (r = ensure_buf(h, h->qinv, (size_t)B)) ||
+        (r = ensure_buf(h, h->qsplit, (size_t)B * h->pitch)) || (r = ensure_buf(h, h->ps_seed_d, (size_t)B * a.k)) ||
+        (r = ensure_buf(h, h->ps_seed_i, (size_t)B * a.k)) || (r = ensure_buf(h, h->ps_thr, (size_t)B)) ||
+        (r = ensure_buf(h, h->ps_pairs, (size_t)4 * pairs)) || (r = ensure_buf(h, h->ps_tab, (size_t)3 * PART_MAX_P + 8)) ||
+        (r = ensure_buf(h, h->ps_scnt, (size_t)B)) || (r = ensure_buf(h, h->ps_surv, (size_t)B * room)) ||
+        (r = ensure_buf(h, h->ps_stat, 2)) || (r = ensure_buf(h, h->ps_tmp, std::max<size_t>(tb, 16))))
+        return r;
+    if (!h->psev[0])
+        for (hipEvent_t& e : h->psev) HIPCHK(h, hipEventCreate(&e));
+    if (h->xsplit_rows < h->n) {
+        if (h->xsplit_rows == 0) HIPCHK(h, hipMemsetAsync(h->xerr.p, 0, sizeof(float), s));
+        LCHK(h, launch_split_h16(h->vecs, h->xsplit_rows, h->n, h->pitch, h->capn, h->xsplit.p, nullptr, h->xinv.p,
+                                 h->xerr.p, s));
+        h->xsplit_rows = h->n;
+    }
+    LCHK(h, launch_norms(h->qpad.p, 0, B, h->pitch, h->lpr, h->vpl, h->qnorm.p, s));
+    HIPCHK(h, hipMemsetAsync(h->qerr.p, 0, sizeof(float), s));
+    LCHK(h, launch_split_h16(h->qpad.p, 0, B, h->pitch, B, h->qsplit.p, nullptr, h->qinv.p, h->qerr.p, s));
+    if (h->metric == EUCLIDEAN) {
+        HIPCHK(h, hipMemsetAsync(h->xmaxn.p, 0, sizeof(float), s));
+        LCHK(h, launch_max_norm(h->norms, h->n, h->xmaxn.p, s));
+    }
+    HIPCHK(h, hipMemsetAsync(h->ps_stat.p, 0, 16, s));
+    PartScanArgs p{};
+    p.s = a;
+    p.P = P;
+    p.seed = seed;
+    p.room = room;
+    p.pitch = h->pitch;
+    p.qnorm = h->qnorm.p;
+    p.qinv = h->qinv.p;
+    p.Qh = h->qsplit.p;
+    p.ldQ = B;
+    p.Xh = h->xsplit.p;
+    p.ldX = h->capn;
+    p.xinv = h->xinv.p;
+    exact_cert_consts(h, 1.0, 0.0, p.c);  // (fp16 1-product: both roundings are the measured xerr / qerr)
+    p.c.xmax = h->xmaxn.p;
+    p.c.xerr = h->xerr.p;
+    p.c.qerr = h->qerr.p;
+    p.seed_d = h->ps_seed_d.p;
+    p.seed_i = h->ps_seed_i.p;
+    p.thr = h->ps_thr.p;
+    p.pkey = h->ps_pairs.p;
+    p.pval = p.pkey + pairs;
+    p.skey = p.pval + pairs;
+    p.sval = p.skey + pairs;
+    p.poff = h->ps_tab.p;
+    p.ibase = p.poff + PART_MAX_P + 2;
+    p.live = p.ibase + PART_MAX_P + 1;
+    p.scnt = h->ps_scnt.p;
+    p.surv = h->ps_surv.p;
+    p.stat = h->ps_stat.p;
+    p.temp = h->ps_tmp.p;
+    p.temp_bytes = h->ps_tmp.n;
+    LCHK(h, launch_part_scan_seed(p, h->lpr, h->vpl, s));
+    if (timing) HIPCHK(h, hipEventRecord(h->psev[0], s));
+    LCHK(h, launch_part_scan_invert(p, s));
+    LCHK(h, launch_part_scan_tiles(p, s));
+    if (timing) HIPCHK(h, hipEventRecord(h->psev[1], s));
+    LCHK(h, launch_part_scan_finish(p, h->lpr, h->vpl, s));
+    h->part_scan_queries = B;
+    h->have_part_scan_timing = timing;
     return 0;
 }
 

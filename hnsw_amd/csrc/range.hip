@@ -26,6 +26,7 @@
 
 #include <algorithm>
 
+#include "cert.hpp"
 #include "device_search.hpp"
 #include "engine.hpp"
 
@@ -66,26 +67,8 @@ __global__ void k_range_thr(RangeArgs a, const float* __restrict__ qnorm, const 
     } else if (!fused || qinv[b] != qinv[b]) {
         st = 1;
     } else {
-        const double xe = c.xerr ? (double)*c.xerr : 0.0, qe = c.qerr ? (double)*c.qerr : 0.0;
-        double td;
-        if (a.g.metric == COSINE) {
-            // k_rerank: |score - d| <= eps_cos + ex
-            const double ex = 1.01 * (1.0 + 1e-4) * (xe + qe + xe * qe);
-            td = (double)r + (double)c.eps_cos + ex;
-        } else {
-            // k_rerank: |score - d^2| <= delta(q); d = sqrtf(s) <= r only if s <= r^2 (1 + 2^-23 + ..)
-            const double qnd = qnorm[b], xm = *c.xmax;
-            const double ed = c.eps_dot + 1.01 * (xe + qe + xe * qe);
-            const double delta = 2.0 * ed * qnd * xm + c.c_l2 * (qnd + xm) * (qnd + xm);
-            td = (double)r * (double)r * (1.0 + 0x1p-22) + delta;
-        }
-        t = (float)td;
-        if ((double)t < td)  // round up
-            t = t > 0.f ? __uint_as_float(__float_as_uint(t) + 1u) : t < 0.f ? __uint_as_float(__float_as_uint(t) - 1u) : 1e-45f;
-        if (!isfinite(t)) {
-            st = 1;
-            t = nan;
-        }
+        t = cert_score_thr(a.g.metric, r, qnorm[b], c);
+        if (t != t) st = 1;
     }
     thr[b] = t;
     a.state[b] = (uint8_t)st;

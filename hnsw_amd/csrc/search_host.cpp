@@ -328,6 +328,18 @@ int exact_k_check(mhnsw_index* h, int k) {
     return exact_k_limit(h, k, wide);
 }
 
+// certificate constants (u = 2^-24; gamma_n = n u / (1 - n u) bounds any
+// order of n-term f32 summation relative to the sum of magnitudes)
+void exact_cert_consts(const mhnsw_index* h, double products, double e_split, CertArgs& cert) {
+    const double u = std::ldexp(1.0, -24);
+    auto gam = [&](double nn) { return nn * u / (1.0 - nn * u); };
+    const double g_mfma = gam(products * h->pitch + 1);
+    const double g_can = gam(4.0 * h->vpl + 8);  // canonical: 4*VPL fmaf per lane + 6 butterfly levels
+    cert.eps_cos = (float)(1.01 * ((g_mfma + e_split + g_can) * (1.0 + 1e-4) + 16 * u));
+    cert.eps_dot = (float)(1.01 * (g_mfma + e_split + g_can));
+    cert.c_l2 = (float)(1.01 * (2.0 * gam(4.0 * h->vpl + 10) + 16 * u));
+}
+
 // the exact path's workspace, the rows it skips and the certificate constants
 // (expect > 0, a range search: the regions and sub-buckets are sized for that many passing
 // rows per query over the whole index instead of J over the sample)
@@ -446,25 +458,17 @@ static int exact_prepare(mhnsw_index* h, const SearchCall& c, const RowSet& rs, 
     const uint8_t* xdead;
     if ((r = exact_skipped(h, s, xdead))) return r;
     g.dead = xdead;
-    // certificate constants (u = 2^-24; gamma_n = n u / (1 - n u) bounds any
-    // order of n-term f32 summation relative to the sum of magnitudes)
-    const double u = std::ldexp(1.0, -24);
-    auto gam = [&](double nn) { return nn * u / (1.0 - nn * u); };
     // products per element: f32 1, bf16x3 3, fp16 2-product 2, fp16 1-product 1.  Split
     // error: bf16x3 drops ql.xl and the planes' tails (3.02 * 2^-16); fp16 2-product
     // rounds the rows to fp16 (2^-11 |x|, Cauchy-Schwarz) and the queries to hi + lo
     // (2^-21); fp16 1-product rounds both once
-    const double g_mfma = gam((h1 ? 1.0 : h2 ? 2.0 : split ? 3.0 : 1.0) * h->pitch + 1);
     // (fp16: the rows' part -- and the queries' in the 1-product -- is the measured
     // max |x' - x| / |x| <= 2^-11, added on the device)
     const double e_split = h1 ? 0.0 : h2 ? std::ldexp(1.0, -21) : split ? 3.02 * std::ldexp(1.0, -16) : 0.0;
-    const double g_can = gam(4.0 * h->vpl + 8);  // canonical: 4*VPL fmaf per lane + 6 butterfly levels
     CertArgs cert{};
+    exact_cert_consts(h, h1 ? 1.0 : h2 ? 2.0 : split ? 3.0 : 1.0, e_split, cert);
     cert.qnorm = h->qnorm.p;
     cert.xmax = h->xmaxn.p;
-    cert.eps_cos = (float)(1.01 * ((g_mfma + e_split + g_can) * (1.0 + 1e-4) + 16 * u));
-    cert.eps_dot = (float)(1.01 * (g_mfma + e_split + g_can));
-    cert.c_l2 = (float)(1.01 * (2.0 * gam(4.0 * h->vpl + 10) + 16 * u));
     cert.flag = h->xflag.p;
     cert.flagged = h->xflagged.p;
     cert.nflag = h->xnflag.p;
@@ -951,7 +955,13 @@ static int search_part(mhnsw_index* h, SearchCall& c, int nprobe, int32_t* oncan
         HIPCHK(h, hipMemsetAsync(h->part_stat + 1, 0, 8, c.s));
         a.stat = h->part_stat + 1;
     }
-    LCHK(h, launch_part_search(a, h->lpr, h->vpl, c.s));
+    h->part_scan_queries = 0;  // last_part_scan_* describe this search
+    h->have_part_scan_timing = false;
+    if (part_scan_wanted(h, c.B, nprobe)) {
+        if ((r = part_scan_search(h, a, c.timing, c.s))) return r;
+    } else {
+        LCHK(h, launch_part_search(a, h->lpr, h->vpl, c.s));
+    }
     if (c.timing) HIPCHK(h, hipEventRecord(h->ev1, c.s));
     if (!c.on_device) HIPCHK(h, hipMemcpyAsync(oncand, h->part_ncand.p, (size_t)c.B * 4, hipMemcpyDeviceToHost, c.s));
     return finish(h, c);

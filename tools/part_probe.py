@@ -12,8 +12,12 @@
             against the exact search; the session's exact and LSH (8 x 16) times alongside.
             --graph builds the bench graph instead of a flat store and adds beam ef 64.
 
+  --scan    the search cases again with part_scan 0 and 1 alternating on the same handle, at
+            part_scan_seed 1 and 2: kernel ms of both, survivors per query, fallback queries
+            and the inversion + scan kernel's share (last_part_scan_ns) -> <out>/part_scan.txt
+
 Writes <out>/partitions.txt and .json.
-Usage: python tools/part_probe.py [--out profiles] [--nbase N] [--graph]"""
+Usage: python tools/part_probe.py [--out profiles] [--nbase N] [--graph] [--scan]"""
 import argparse
 import json
 import os
@@ -32,6 +36,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
 ap.add_argument("--nbase", type=int, default=1_000_000)
 ap.add_argument("--graph", action="store_true")
+ap.add_argument("--scan", action="store_true")
 args = ap.parse_args()
 
 dev = torch.device("cuda")
@@ -100,6 +105,23 @@ for m in (1, 8, 32):
     hit = np.mean([len(set(r[0][i, : r[2][i]]) & set(er[0][i])) / K for i in range(B)])
     rec["search"].append(dict(nprobe=m, kernel_ms=ms, ncand_mean=float(r[3].mean()), ncand_max=int(r[3].max()),
                               recall=float(hit)))
+if args.scan:  # the same cases, the walk and the partition-major scan alternating on this handle
+    rec["scan"] = []
+    for seed in (1, 2):
+        for m in (1, 8, 32):
+            row = dict(nprobe=m, seed=seed)
+            for on in (0, 1):
+                g.set_option("part_scan", on)
+                g.set_option("part_scan_min_b", 1)
+                g.set_option("part_scan_seed", seed)
+                ms, r = best(lambda: g.search_partitions_arrays(Q, K, m))
+                row["scan_ms" if on else "walk_ms"] = ms
+                if on and g.get_option("last_part_scan_queries"):
+                    row.update(pairs_per_query=g.get_option("last_part_scan_pairs") / B,
+                               fallback=g.get_option("last_part_scan_fallback_queries"),
+                               invert_tiles_ms=g.get_option("last_part_scan_ns") / 1e6)
+            rec["scan"].append(row)
+    g.set_option("part_scan", 0)
 g.close()
 
 lines = ["Partitions on the bench rows: %d x %d cosine, k = %d, B = %d" % (n, d, K, B), "",
@@ -123,6 +145,16 @@ for s in rec["search"]:
                  (s["nprobe"], s["kernel_ms"], s["ncand_mean"], s["ncand_max"], s["recall"]))
 print("\n".join(lines))
 os.makedirs(args.out, exist_ok=True)
+if args.scan:
+    sl = ["Partition scan on the bench rows: %d x %d cosine, P = 1024, k = %d, B = %d; exact top-10 %.2f ms" %
+          (n, d, K, B, b["exact_ms"])]
+    for s in rec["scan"]:
+        sl.append("seed %d nprobe %2d: walk %8.2f ms, scan %8.2f ms" % (s["seed"], s["nprobe"], s["walk_ms"], s["scan_ms"]) +
+                  (" (inversion + tiles %.2f ms), %.1f survivors per query, %d fallback queries" %
+                   (s["invert_tiles_ms"], s["pairs_per_query"], s["fallback"]) if "fallback" in s else " (the walk ran)"))
+    print("\n".join(sl))
+    with open(os.path.join(args.out, "part_scan.txt"), "w") as fh:
+        fh.write("\n".join(sl) + "\n")
 with open(os.path.join(args.out, "partitions.txt"), "w") as fh:
     fh.write("\n".join(lines) + "\n")
 with open(os.path.join(args.out, "partitions.json"), "w") as fh:
