@@ -1508,9 +1508,12 @@ int mhnsw_set_option(mhnsw_index* h, const char* name, int64_t v) {
     } else if (n == "part_scan_min_b") {
         if (v < 1 || v > INT32_MAX) return fail(h, MHNSW_EINVAL, "part_scan_min_b must be >= 1");
         h->part_scan_min_b = (int)v;
-    } else if (n == "part_scan_seed") {  // (a search covers at most nprobe - 1 with it)
-        if (v < 1 || v >= PART_MAX_PROBE) return fail(h, MHNSW_EINVAL, "part_scan_seed must be in [1, %d]", PART_MAX_PROBE - 1);
+    } else if (n == "part_scan_seed") {  // (a search covers at most nprobe - 1 with it; 0: the radius from the scan)
+        if (v < 0 || v >= PART_MAX_PROBE) return fail(h, MHNSW_EINVAL, "part_scan_seed must be in [0, %d]", PART_MAX_PROBE - 1);
         h->part_scan_seed = (int)v;
+    } else if (n == "part_scan_seed_room") {
+        if (v < 1 || v > (1 << 20)) return fail(h, MHNSW_EINVAL, "part_scan_seed_room must be in [1, %d]", 1 << 20);
+        h->part_scan_seed_room = (int)v;
     } else if (n == "part_scan_room") {
         if (v < 1 || v > (1 << 20)) return fail(h, MHNSW_EINVAL, "part_scan_room must be in [1, %d]", 1 << 20);
         h->part_scan_room = (int)v;
@@ -1725,6 +1728,7 @@ int mhnsw_get_option(const mhnsw_index* h, const char* name, int64_t* v) {
     else if (n == "part_scan_min_b") *v = h->part_scan_min_b;
     else if (n == "part_scan_seed") *v = h->part_scan_seed;
     else if (n == "part_scan_room") *v = h->part_scan_room;
+    else if (n == "part_scan_seed_room") *v = h->part_scan_seed_room;
     else if (n == "last_part_scan_queries") *v = h->part_scan_queries;
     else if (n == "last_part_scan_pairs" || n == "last_part_scan_fallback_queries") {
         unsigned long long st[2] = {0, 0};

@@ -611,6 +611,10 @@ int launch_part_search(const PartSearchArgs& a, int lpr, int vpl, hipStream_t s)
 // items' prefix), tiles (k_part_scan: survivors per query), finish (the survivors ranked
 // canonically onto the seed list; a query without a threshold, or whose survivors overflowed,
 // walks all its probes).
+// seed = 0: no walk.  The launches are invert (seed_pass = 1: probe 0 of every query that can
+// have a threshold), seed_tiles (k_part_seed_scan: the nearest list's scores per query), pick
+// (k_ps_pick: the k best-scored rows evaluated canonically -> the threshold, an empty list), then
+// invert (all probes), tiles and finish as above.
 constexpr int PSCAN_BM = 64, PSCAN_BN = 128;  // k_part_scan's tile: queries x rows
 struct PartScanArgs {
     PartSearchArgs s;       // the walk's arguments and the call's outputs
@@ -639,11 +643,17 @@ struct PartScanArgs {
     unsigned long long* stat;  // [0] += survivors ranked, [1] += queries that walked
     void* temp;
     size_t temp_bytes;
+    // part_scan_seed = 0
+    int seed_pass;          // 1: the inversion and the tiles of the seed scan (probe 0 alone)
+    int seed_room;          // scores per query the seed scan holds
+    float* sscore;          // [B * seed_room] score of position j of the query's nearest list
 };
 int part_scan_temp_bytes(int64_t pairs, size_t* bytes);
 int launch_part_scan_seed(const PartScanArgs& a, int lpr, int vpl, hipStream_t s);
 int launch_part_scan_invert(const PartScanArgs& a, hipStream_t s);
 int launch_part_scan_tiles(const PartScanArgs& a, hipStream_t s);
+int launch_part_scan_seed_tiles(const PartScanArgs& a, hipStream_t s);
+int launch_part_scan_pick(const PartScanArgs& a, int lpr, int vpl, hipStream_t s);
 int launch_part_scan_finish(const PartScanArgs& a, int lpr, int vpl, hipStream_t s);
 
 // ---- wide exact search (wide.hip): exact top-k past k 256 through the range pipeline ----

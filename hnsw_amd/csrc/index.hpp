@@ -373,12 +373,13 @@ struct mhnsw_index {
     hipEvent_t pev[4] = {};       // around the last list rebuild, around the last Train
     bool have_part_rebuild = false, have_part_train = false;
     // The partition-major scan (part_scan.hip; part_host.cpp part_scan_search): the options
-    // "part_scan", "part_scan_min_b", "part_scan_seed", "part_scan_room"; the seed lists, the
-    // thresholds, the (partition, query) pairs and their sorted copy, the per-partition tables,
+    // "part_scan", "part_scan_min_b", "part_scan_seed", "part_scan_room", "part_scan_seed_room";
+    // the seed lists, the thresholds, the seed scan's score rows (part_scan_seed = 0), the
+    // (partition, query) pairs and their sorted copy, the per-partition tables,
     // the survivors with their counts, the counters {survivors ranked, queries that walked};
     // the queries the last partition search sent through the scan; events around its kernels.
-    int part_scan = 0, part_scan_min_b = 64, part_scan_seed = 1, part_scan_room = 1024;
-    DevBuf<float> ps_seed_d, ps_thr;
+    int part_scan = 0, part_scan_min_b = 64, part_scan_seed = 1, part_scan_room = 1024, part_scan_seed_room = 4096;
+    DevBuf<float> ps_seed_d, ps_thr, ps_sscore;
     DevBuf<uint32_t> ps_seed_i, ps_pairs, ps_scnt, ps_surv;
     DevBuf<int32_t> ps_tab;
     DevBuf<uint8_t> ps_tmp;

@@ -82,6 +82,7 @@ void part_free(mhnsw_index* h) {
     h->part_key.n = h->part_val.n = h->part_skey.n = h->part_sid.n = h->part_tmp.n = h->part_partial.n = 0;
     F(h->ps_seed_d.p);
     F(h->ps_thr.p);
+    F(h->ps_sscore.p);
     F(h->ps_seed_i.p);
     F(h->ps_pairs.p);
     F(h->ps_scnt.p);
@@ -90,7 +91,7 @@ void part_free(mhnsw_index* h) {
     F(h->ps_tmp.p);
     F(h->ps_stat.p);
     h->ps_seed_d.n = h->ps_thr.n = h->ps_seed_i.n = h->ps_pairs.n = h->ps_scnt.n = h->ps_surv.n = 0;
-    h->ps_tab.n = h->ps_tmp.n = h->ps_stat.n = 0;
+    h->ps_tab.n = h->ps_tmp.n = h->ps_stat.n = h->ps_sscore.n = 0;
     h->have_part_scan_timing = false;
     for (hipEvent_t& e : h->pev) {
         if (e) (void)hipEventDestroy(e);
@@ -322,10 +323,11 @@ static int part_rebalance(mhnsw_index* h, int64_t* moved) {
 }
 
 // ---- the partition-major scan (part_scan.hip; DESIGN.md §6 "Partition scan") ----
-// Option "part_scan": from part_scan_min_b queries and two probes on.  (The items' count is a
-// 32-bit prefix: a shape whose bound on it does not fit keeps the walk.)
+// Option "part_scan": from part_scan_min_b queries and two probes on -- one probe at
+// part_scan_seed = 0, where no probe is kept for a seed walk.  (The items' count is a 32-bit
+// prefix: a shape whose bound on it does not fit keeps the walk.)
 bool part_scan_wanted(const mhnsw_index* h, int64_t B, int nprobe) {
-    if (!h->part_scan || nprobe < 2 || B < h->part_scan_min_b) return false;
+    if (!h->part_scan || nprobe < (h->part_scan_seed == 0 ? 1 : 2) || B < h->part_scan_min_b) return false;
     const int64_t qt = B * nprobe / PSCAN_BM + h->part_P, rt = h->part_list_n / PSCAN_BN + 1;
     return B * nprobe < ((int64_t)1 << 31) && qt * rt < ((int64_t)1 << 31);
 }
@@ -339,9 +341,13 @@ int part_scan_search(mhnsw_index* h, const PartSearchArgs& a, bool timing, hipSt
     const int64_t B = a.B;
     const int nprobe = a.nprobe, P = h->part_P;
     const int seed = std::min(h->part_scan_seed, nprobe - 1), room = h->part_scan_room;
+    // (no list is longer than the rows the lists hold: the score rows need no more)
+    const int seed_room = (int)std::min<int64_t>(h->part_scan_seed_room, std::max<int64_t>(a.n, 1));
     const int64_t pairs = B * (nprobe - seed);
-    size_t tb = 0;
-    if (part_scan_temp_bytes(pairs, &tb)) return fail(h, MHNSW_EDEVICE, "radix sort sizing failed");
+    size_t tb = 0, tb0 = 0;
+    if (part_scan_temp_bytes(pairs, &tb) || (seed == 0 && part_scan_temp_bytes(B, &tb0)))
+        return fail(h, MHNSW_EDEVICE, "radix sort sizing failed");
+    tb = std::max(tb, tb0);
     const int64_t plane = h->capn * h->pitch;
     if (h->xsplit.n < (size_t)plane * 2 || h->xsplit_plane != plane || h->xsplit_kind != 2) {
         if ((r = ensure_buf(h, h->xsplit, (size_t)plane * 2))) return r;
@@ -355,7 +361,8 @@ int part_scan_search(mhnsw_index* h, const PartSearchArgs& a, bool timing, hipSt
         (r = ensure_buf(h, h->ps_seed_i, (size_t)B * a.k)) || (r = ensure_buf(h, h->ps_thr, (size_t)B)) ||
         (r = ensure_buf(h, h->ps_pairs, (size_t)4 * pairs)) || (r = ensure_buf(h, h->ps_tab, (size_t)3 * PART_MAX_P + 8)) ||
         (r = ensure_buf(h, h->ps_scnt, (size_t)B)) || (r = ensure_buf(h, h->ps_surv, (size_t)B * room)) ||
-        (r = ensure_buf(h, h->ps_stat, 2)) || (r = ensure_buf(h, h->ps_tmp, std::max<size_t>(tb, 16))))
+        (r = ensure_buf(h, h->ps_stat, 2)) || (r = ensure_buf(h, h->ps_tmp, std::max<size_t>(tb, 16))) ||
+        (seed == 0 && (r = ensure_buf(h, h->ps_sscore, (size_t)B * seed_room))))
         return r;
     if (!h->psev[0])
         for (hipEvent_t& e : h->psev) HIPCHK(h, hipEventCreate(&e));
@@ -405,8 +412,19 @@ int part_scan_search(mhnsw_index* h, const PartSearchArgs& a, bool timing, hipSt
     p.stat = h->ps_stat.p;
     p.temp = h->ps_tmp.p;
     p.temp_bytes = h->ps_tmp.n;
-    LCHK(h, launch_part_scan_seed(p, h->lpr, h->vpl, s));
-    if (timing) HIPCHK(h, hipEventRecord(h->psev[0], s));
+    if (seed == 0) {  // the radius from the scan: the nearest lists scored, k rows of each evaluated
+        p.seed_room = seed_room;
+        p.sscore = h->ps_sscore.p;
+        if (timing) HIPCHK(h, hipEventRecord(h->psev[0], s));
+        PartScanArgs p0 = p;
+        p0.seed_pass = 1;
+        LCHK(h, launch_part_scan_invert(p0, s));
+        LCHK(h, launch_part_scan_seed_tiles(p0, s));
+        LCHK(h, launch_part_scan_pick(p, h->lpr, h->vpl, s));
+    } else {
+        LCHK(h, launch_part_scan_seed(p, h->lpr, h->vpl, s));
+        if (timing) HIPCHK(h, hipEventRecord(h->psev[0], s));
+    }
     LCHK(h, launch_part_scan_invert(p, s));
     LCHK(h, launch_part_scan_tiles(p, s));
     if (timing) HIPCHK(h, hipEventRecord(h->psev[1], s));

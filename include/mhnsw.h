@@ -428,19 +428,27 @@ int mhnsw_search_lsh_device(mhnsw_index *h, const float *d_queries, int64_t B, i
  * host-pointer search), last_part_rebuild_ns, last_part_train_ns.
  * The partition-major scan (DESIGN.md "Partition scan"), a second way of running
  * mhnsw_search_part / _device with the same results bit for bit.  Options:
- * part_scan 0 (default: the one-wave walk) or 1: the scan when nprobe >= 2 and
- * B >= part_scan_min_b, else the walk ("part_scan must be 0 or 1").
+ * part_scan 0 (default: the one-wave walk) or 1: the scan when nprobe >= 2
+ * (nprobe >= 1 at part_scan_seed 0) and B >= part_scan_min_b, else the walk
+ * ("part_scan must be 0 or 1").
  * part_scan_min_b >= 1, default 64: NOT MEASURED, a placeholder until the batch
  * sweep of tools/part_probe.py --scan has run on the device.
- * part_scan_seed >= 1, default 1: each query's nearest partitions that the seed
- * walk covers (a search uses at most nprobe - 1).  part_scan_room >= 1, default
- * 1024: survivor slots per query; a query with more is answered by the walk.
+ * part_scan_seed in [0, 255], default 1: each query's nearest partitions that the
+ * seed walk covers (a search uses at most nprobe - 1).  0: no partition is walked;
+ * the nearest partition is scored by the scan too, and the radius is the largest
+ * canonical distance of its k best-scored rows.  part_scan_seed_room in
+ * [1, 2^20], default 4096 (NOT MEASURED, a memory placeholder of B x room x 4
+ * bytes): the rows of a query's nearest list that seed 0 holds scores for; a
+ * query whose nearest list is longer is answered by the walk.  part_scan_room
+ * >= 1, default 1024: survivor slots per query (at seed 0 the nearest
+ * partition's survivors count too); a query with more is answered by the walk.
  * Read-only, of the last partition search: last_part_scan_queries (the queries
  * sent through the scan, 0 when the walk ran), last_part_scan_pairs (the (query,
  * row) survivors the canonical pass ranked), last_part_scan_fallback_queries (the
  * queries of the scan answered by the walk: survivors past the room, or no usable
  * threshold), last_part_scan_ns (device time of the inversion and the scan
- * kernel; the seed walk and the finish are the rest of the search's time). */
+ * kernel; the seed walk and the finish are the rest of the search's time.  At
+ * seed 0: everything between the probe order and the finish). */
 int mhnsw_part_enable(mhnsw_index *h, int partitions, uint64_t seed, const float *centroids, int dim);
 int mhnsw_part_assign(mhnsw_index *h, const float *vecs, int64_t n, int dim, int nprobe, int32_t *out_parts);
 int mhnsw_part_rows(mhnsw_index *h, int32_t *out);

@@ -13,8 +13,10 @@
             --graph builds the bench graph instead of a flat store and adds beam ef 64.
 
   --scan    the search cases again with part_scan 0 and 1 alternating on the same handle, at
-            part_scan_seed 1 and 2: kernel ms of both, survivors per query, fallback queries
-            and the inversion + scan kernel's share (last_part_scan_ns) -> <out>/part_scan.txt
+            part_scan_seed 0, 1 and 2: kernel ms of both, survivors per query, fallback queries
+            and the inversion + scan kernel's share (last_part_scan_ns; at seed 0 everything
+            between the probe order and the finish: both inversions, the seed scan, the pick
+            and the tiles) -> <out>/part_scan.txt
 
 Writes <out>/partitions.txt and .json.
 Usage: python tools/part_probe.py [--out profiles] [--nbase N] [--graph] [--scan]"""
@@ -107,7 +109,7 @@ for m in (1, 8, 32):
                               recall=float(hit)))
 if args.scan:  # the same cases, the walk and the partition-major scan alternating on this handle
     rec["scan"] = []
-    for seed in (1, 2):
+    for seed in (0, 1, 2):
         for m in (1, 8, 32):
             row = dict(nprobe=m, seed=seed)
             for on in (0, 1):
@@ -150,8 +152,8 @@ if args.scan:
           (n, d, K, B, b["exact_ms"])]
     for s in rec["scan"]:
         sl.append("seed %d nprobe %2d: walk %8.2f ms, scan %8.2f ms" % (s["seed"], s["nprobe"], s["walk_ms"], s["scan_ms"]) +
-                  (" (inversion + tiles %.2f ms), %.1f survivors per query, %d fallback queries" %
-                   (s["invert_tiles_ms"], s["pairs_per_query"], s["fallback"]) if "fallback" in s else " (the walk ran)"))
+                  (" (%s %.2f ms), %.1f survivors per query, %d fallback queries" %
+                   ("inversion + tiles" if s["seed"] else "seed scan + pick + inversions + tiles", s["invert_tiles_ms"], s["pairs_per_query"], s["fallback"]) if "fallback" in s else " (the walk ran)"))
     print("\n".join(sl))
     with open(os.path.join(args.out, "part_scan.txt"), "w") as fh:
         fh.write("\n".join(sl) + "\n")
